@@ -74,7 +74,99 @@ def parse_args(argv=None):
         help="print a per-phase mean breakdown (evict/fabric-off/stage/"
         "reset/verify/reschedule) to stderr after the timed region",
     )
-    return p.parse_args(argv)
+    p.add_argument(
+        "--dump-outputs",
+        default="",
+        metavar="DIR",
+        help="after the timed steps, write what the last timed step "
+        "computed (device modes, node labels, attestation numerics) as "
+        "DIR/<name>.npy (float64) so two builds can be compared",
+    )
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also report everything beyond the headline figure (today: "
+        "the per-phase breakdown of --phase-report); a plain run only "
+        "sets up, warms up, times the steps and prints the result line",
+    )
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    if args.warmup < 0:
+        p.error("--warmup must be >= 0")
+    return args
+
+
+#: numeric codes of the label / mode vocabularies in the dumped arrays
+_MODE_CODES = {"off": 0.0, "on": 1.0, "devtools": 2.0, "ppcie": 3.0}
+_READY_CODES = {"": 0.0, "false": 1.0, "true": 2.0, "emulated": 3.0}
+
+#: columns of attest_report.npy (one row per managed GPU). Only the
+#: deterministic fields of the probe report: timings and rates vary from
+#: run to run and are left out. The 64-bit GEMM checksum is split into
+#: four 16-bit words (most significant first) so float64 holds it exactly.
+ATTEST_COLUMNS = (
+    "ok", "gemm_dim", "cu_count", "max_abs_err", "fp8_max_abs_err",
+    "lds_failures", "checksum_w3", "checksum_w2", "checksum_w1",
+    "checksum_w0", "peers_attempted", "peers_verified",
+)
+
+
+def dump_outputs(out_dir, devices, node, attest_reports) -> None:
+    """Write the results of the last timed step as ``<name>.npy``.
+
+    - ``device_modes``  [n_gpus, 2]: CC mode and fabric mode read back
+      from every managed device (``_MODE_CODES``).
+    - ``node_labels``   [3]: cc.mode.state, cc.ready.state
+      (``_READY_CODES``; -1 = unknown value) and the cordon flag.
+    - ``attest_report`` [n_gpus, 12]: ``ATTEST_COLUMNS`` of the probe
+      report each device's verify phase produced (GPU tiers only).
+    """
+    import numpy as np
+
+    from k8s_cc_manager_amd.labels import CC_READY_LABEL, CC_STATE_LABEL
+
+    os.makedirs(out_dir, exist_ok=True)
+    modes = np.array(
+        [
+            [
+                _MODE_CODES.get(d.query_cc_mode(), -1.0),
+                _MODE_CODES.get(d.query_fabric_mode(), -1.0),
+            ]
+            for d in devices
+        ],
+        dtype=np.float64,
+    ).reshape(len(devices), 2)
+    np.save(os.path.join(out_dir, "device_modes.npy"), modes)
+
+    labels = node["metadata"].get("labels") or {}
+    node_labels = np.array(
+        [
+            _MODE_CODES.get(labels.get(CC_STATE_LABEL, ""), -1.0),
+            _READY_CODES.get(labels.get(CC_READY_LABEL, ""), -1.0),
+            1.0 if (node.get("spec") or {}).get("unschedulable") else 0.0,
+        ],
+        dtype=np.float64,
+    )
+    np.save(os.path.join(out_dir, "node_labels.npy"), node_labels)
+
+    if attest_reports:
+        rows = []
+        for idx in sorted(attest_reports):
+            rep = attest_reports[idx]
+            rows.append(
+                [
+                    float(rep.ok), rep.gemm_dim, rep.cu_count,
+                    rep.max_abs_err, rep.fp8_max_abs_err, rep.lds_failures,
+                    (rep.checksum >> 48) & 0xFFFF, (rep.checksum >> 32) & 0xFFFF,
+                    (rep.checksum >> 16) & 0xFFFF, rep.checksum & 0xFFFF,
+                    rep.peers_attempted, rep.peers_verified,
+                ]
+            )
+        np.save(
+            os.path.join(out_dir, "attest_report.npy"),
+            np.array(rows, dtype=np.float64),
+        )
 
 
 def main(argv=None) -> int:
@@ -191,6 +283,23 @@ def main(argv=None) -> int:
         attestor = None
         device_tier = "mock"
 
+    # keep the raw probe report of each device's latest attestation (the
+    # attestor hook hands the engine only a rounded summary); one dict
+    # store per probe, with or without --dump-outputs, so the timed path
+    # is the same either way
+    attest_reports: dict = {}
+    if use_gpu:
+        _attest_device = attest.attest_device
+
+        def _attest_and_keep(device_index, gemm_dim=1024):
+            rep = _attest_device(device_index, gemm_dim=gemm_dim)
+            attest_reports[device_index] = rep
+            return rep
+
+        attest.attest_device = _attest_and_keep
+
+    phase_report = args.phase_report or args.full
+
     barrier = DistFabricBarrier() if world > 1 else None
     engine = TransitionEngine(attestor=attestor, barrier=barrier)
     manager = CCManager(
@@ -252,7 +361,7 @@ def main(argv=None) -> int:
         ok = manager.apply_mode(manager.with_default(label))
         if not ok:
             raise RuntimeError(f"rank {rank}: reconcile step {i} failed")
-        if timed and args.phase_report and manager.last_report is not None:
+        if timed and phase_report and manager.last_report is not None:
             phase_n[0] += 1
             for k, v in manager.last_report.phases.items():
                 phase_acc[k] = phase_acc.get(k, 0.0) + v
@@ -279,7 +388,7 @@ def main(argv=None) -> int:
     sync()
     elapsed = time.perf_counter() - t0
 
-    if args.phase_report and rank == 0 and phase_n[0]:
+    if phase_report and rank == 0 and phase_n[0]:
         means = {k: round(v / phase_n[0] * 1e3, 3) for k, v in sorted(phase_acc.items())}
         accounted = sum(means.values())
         print(
@@ -291,6 +400,13 @@ def main(argv=None) -> int:
                 }
             ),
             file=sys.stderr,
+        )
+
+    if args.dump_outputs and rank == 0:
+        devices, _ = backend_dev.find_devices()
+        dump_outputs(
+            args.dump_outputs, devices, cluster.get_node_copy(node_name),
+            attest_reports,
         )
 
     # max over ranks
@@ -343,6 +459,8 @@ def main(argv=None) -> int:
         workload_stop.set()
         workload_thread.join(timeout=10)
     cluster.stop()
+    if use_gpu:
+        attest.attest_device = _attest_device
     if world > 1:
         dist.destroy_process_group()
     return 0

@@ -45,3 +45,65 @@ def test_bench_cpu_mock(tmp_path):
     # the stdout JSON line is parseable too
     json_lines = [l for l in proc.stdout.splitlines() if l.startswith("{")]
     assert json_lines and json.loads(json_lines[-1])["value"] > 0
+    # a plain run reports the headline only: no per-phase breakdown
+    assert result["ms_per_step"] > 0
+    assert "phase_ms_mean" not in proc.stderr
+
+
+def _run_inprocess(argv, capsys):
+    import bench  # the repository root is on sys.path (conftest.py)
+
+    assert bench.main(argv) == 0
+    return capsys.readouterr()
+
+
+def test_dump_outputs_mock(tmp_path, capsys):
+    """--dump-outputs writes the last timed step's results as float64
+    .npy files, identical from run to run."""
+    import numpy as np
+
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        _run_inprocess(
+            ["--mock", "--gpus", "2", "--steps", "2", "--warmup", "1",
+             "--dump-outputs", str(d)],
+            capsys,
+        )
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ["device_modes.npy", "node_labels.npy"]
+        dumps.append({f: np.load(d / f) for f in files})
+    a, b = dumps
+    for f in a:
+        assert a[f].dtype == np.float64
+        assert np.array_equal(a[f], b[f])
+    # steps 0..2 alternate on/off/on: the last timed step left CC on,
+    # fabric off, labels on/true, node uncordoned
+    assert a["device_modes.npy"].tolist() == [[1.0, 0.0], [1.0, 0.0]]
+    assert a["node_labels.npy"].tolist() == [1.0, 2.0, 0.0]
+
+    # one step fewer ends on "off": --steps really sets the step count
+    d = tmp_path / "c"
+    _run_inprocess(
+        ["--mock", "--gpus", "1", "--steps", "1", "--warmup", "1",
+         "--dump-outputs", str(d)],
+        capsys,
+    )
+    assert np.load(d / "device_modes.npy").tolist() == [[0.0, 0.0]]
+    assert np.load(d / "node_labels.npy").tolist() == [0.0, 1.0, 0.0]
+
+
+def test_full_adds_phase_breakdown(capsys):
+    """--full carries everything beyond the headline figure."""
+    cap = _run_inprocess(
+        ["--mock", "--steps", "2", "--warmup", "1", "--full"], capsys
+    )
+    result = json.loads(
+        [l for l in cap.out.splitlines() if l.startswith("{")][-1]
+    )
+    assert result["metric"] == "reconcile_gpus_per_sec"
+    assert result["steps"] == 2 and result["ms_per_step"] > 0
+    phase = json.loads(
+        [l for l in cap.err.splitlines() if l.startswith('{"phase_ms_mean"')][-1]
+    )
+    assert phase["phase_ms_mean"] and phase["step_ms"] > 0

@@ -23,15 +23,21 @@ def test_midstream_compaction_emits_410():
     rv = k8s.get_node(NODE)["metadata"]["resourceVersion"]
 
     seen = []
+    burst_done = threading.Event()
 
     def watcher():
         # deliberately SLOW consumer: backpressure lets the server-side
-        # event log trim past this watcher's cursor
+        # event log trim past this watcher's cursor. Once the burst is
+        # over the damage is done, so drain what the socket buffers still
+        # hold at full speed: the 410 is queued BEHIND those events, and
+        # a consumer that stays slow can run out of time before it gets
+        # there (seen as a flake on boxes with large socket buffers).
         for event in k8s.watch_node(NODE, resource_version=rv, timeout_seconds=30):
             seen.append(event)
             if event.get("type") == "ERROR":
                 return
-            time.sleep(0.005)
+            if not burst_done.is_set():
+                time.sleep(0.005)
 
     t = threading.Thread(target=watcher)
     t.start()
@@ -39,12 +45,13 @@ def test_midstream_compaction_emits_410():
     # Burst enough churn BYTES that the server-side handler must block
     # on the socket (the consumer is slower than the producer): kernel
     # socket buffers can absorb hundreds of KB, so the burst has to be
-    # megabytes — a small burst fits in the buffers, the handler never
-    # falls behind the trim, and no 410 is provoked (seen as a flake on
-    # fast boxes).
-    pad = "x" * 120
+    # tens of megabytes — a small burst fits in the buffers, the handler
+    # never falls behind the trim, and no 410 is provoked (seen as a
+    # flake on fast boxes).
+    pad = "x" * 1200
     for i in range(30000):
         cluster.set_node_label(NODE, "churn", f"{pad}{i}")
+    burst_done.set()
     t.join(timeout=60)
     cluster.stop()
     assert any(
