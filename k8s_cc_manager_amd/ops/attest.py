@@ -13,7 +13,7 @@ import ctypes
 import logging
 import os
 import re
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 from pathlib import Path
 from typing import Optional
 
@@ -93,33 +93,19 @@ class AttestReport:
 
     @classmethod
     def from_c(cls, c: _CReport) -> "AttestReport":
+        """Copy every same-named field of the C report; only the fields
+        whose Python form differs are spelled out."""
+        special = {
+            "arch": c.arch.decode(errors="replace"),
+            "error": c.error.decode(errors="replace"),
+            "gemm_dim": c.gemm_m,
+            "ok": bool(c.ok),
+        }
         return cls(
-            device=c.device,
-            cu_count=c.cu_count,
-            arch=c.arch.decode(errors="replace"),
-            vram_total_mb=c.vram_total_mb,
-            gemm_dim=c.gemm_m,
-            gemm_ms=c.gemm_ms,
-            gemm_tflops=c.gemm_tflops,
-            ref_ms=c.ref_ms,
-            max_abs_err=c.max_abs_err,
-            checksum=c.checksum,
-            fp8_ms=c.fp8_ms,
-            fp8_tflops=c.fp8_tflops,
-            fp8_max_abs_err=c.fp8_max_abs_err,
-            lds_ms=c.lds_ms,
-            lds_failures=c.lds_failures,
-            hbm_ms=c.hbm_ms,
-            hbm_gbps=c.hbm_gbps,
-            peer_count=c.peer_count,
-            peers_accessible=c.peers_accessible,
-            peers_attempted=c.peers_attempted,
-            peers_verified=c.peers_verified,
-            xgmi_ms=c.xgmi_ms,
-            xgmi_gbps_min=c.xgmi_gbps_min,
-            xgmi_gbps_max=c.xgmi_gbps_max,
-            ok=bool(c.ok),
-            error=c.error.decode(errors="replace"),
+            **{
+                f.name: special[f.name] if f.name in special else getattr(c, f.name)
+                for f in fields(cls)
+            }
         )
 
 
@@ -346,29 +332,33 @@ def attest_device_by_bdf(device) -> dict:
     return summary
 
 
+def _gemm_call(fn_name: str, label: str, *args: int) -> None:
+    """Call one of the library's GEMM entry points; raise on rc != 0."""
+    rc = getattr(_load(), fn_name)(*args)
+    if rc != 0:
+        raise AttestationError(f"{label} rc={rc}")
+
+
 def mfma_gemm_bf16(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
                    m: int, n: int, k: int) -> None:
     """Launch C[M,N] = A[M,K] @ Bt[N,K]^T on caller-owned device buffers
     (torch tensors via .data_ptr()). M,N multiples of 128, K of 32."""
-    rc = _load().cc_mfma_gemm_bf16(device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
-    if rc != 0:
-        raise AttestationError(f"mfma_gemm_bf16 rc={rc}")
+    _gemm_call("cc_mfma_gemm_bf16", "mfma_gemm_bf16",
+               device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
 
 
 def ref_gemm_f32(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
                  m: int, n: int, k: int) -> None:
-    rc = _load().cc_ref_gemm_f32(device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
-    if rc != 0:
-        raise AttestationError(f"ref_gemm_f32 rc={rc}")
+    _gemm_call("cc_ref_gemm_f32", "ref_gemm_f32",
+               device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
 
 
 def mfma_gemm_fp8(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
                   m: int, n: int, k: int) -> None:
     """MX-scaled fp8 e4m3 GEMM (unit scales): C = A @ Bt^T, fp32 out.
     M,N multiples of 256, K of 256."""
-    rc = _load().cc_mfma_gemm_fp8(device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
-    if rc != 0:
-        raise AttestationError(f"mfma_gemm_fp8 rc={rc}")
+    _gemm_call("cc_mfma_gemm_fp8", "mfma_gemm_fp8",
+               device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
 
 
 def mfma_gemm_fp8_variant(device_index: int, a_ptr: int, bt_ptr: int,
@@ -376,16 +366,14 @@ def mfma_gemm_fp8_variant(device_index: int, a_ptr: int, bt_ptr: int,
                           which: int) -> None:
     """Force an fp8 variant: 0=128/BK128 2-blk, 1=256-deep, 2=128/BK256,
     3=BK64 4-blk, 4=BK128 3-blk 1.5-buf, 5=BK128 4-blk 1-buf (default
-    dispatch), 6=256x128 tile 2-blk, 7=producer/consumer wave split
-    (4 stage + 4 MFMA waves, LDS-flag handoff, barrier-free K loop),
-    8-12=instrumentation arms (XCD remap / skew / rotation),
-    13=256-tile 1-blk persistent, 14=split-K (tiny-grid chip filler,
-    hw fp32 atomics)."""
-    rc = _load().cc_mfma_gemm_fp8_variant(
-        device_index, a_ptr, bt_ptr, c_ptr, m, n, k, which
-    )
-    if rc != 0:
-        raise AttestationError(f"mfma_gemm_fp8_variant({which}) rc={rc}")
+    dispatch past 1 block/CU), 6=256x128 tile 2-blk, 7=producer/consumer
+    wave split (4 stage + 4 MFMA waves, LDS-flag handoff, barrier-free
+    K loop; default dispatch up to 1 block/CU), 8-12=instrumentation
+    arms (8=5+XCD remap, 9=7+XCD remap, 10=5+skew, 11=5+rotation,
+    12=5+skew+rotation), 13=256-tile 1-blk persistent, 14=split-K of 5
+    (hw fp32 atomics; measured out of the default dispatch)."""
+    _gemm_call("cc_mfma_gemm_fp8_variant", f"mfma_gemm_fp8_variant({which})",
+               device_index, a_ptr, bt_ptr, c_ptr, m, n, k, which)
 
 
 def mfma_gemm_bf16_variant(device_index: int, a_ptr: int, bt_ptr: int,
@@ -393,8 +381,5 @@ def mfma_gemm_bf16_variant(device_index: int, a_ptr: int, bt_ptr: int,
                            which: int) -> None:
     """Force a GEMM variant: 0 = 128x128 step-3, 1 = 256x256 8-phase,
     2 = 256x256 8-phase 32x32-op, 3 = 128x128 4-blocks/CU 1-buf."""
-    rc = _load().cc_mfma_gemm_bf16_variant(
-        device_index, a_ptr, bt_ptr, c_ptr, m, n, k, which
-    )
-    if rc != 0:
-        raise AttestationError(f"mfma_gemm_bf16_variant({which}) rc={rc}")
+    _gemm_call("cc_mfma_gemm_bf16_variant", f"mfma_gemm_bf16_variant({which})",
+               device_index, a_ptr, bt_ptr, c_ptr, m, n, k, which)

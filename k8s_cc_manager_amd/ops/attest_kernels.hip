@@ -1,42 +1,48 @@
-// CDNA4 (gfx950 / MI355X) post-reset attestation probe.
+// CDNA4 (gfx950 / MI355X) post-reset attestation probe: the C API.
 //
 // The one hand-written kernel family of the AMD CC manager. After a CC
 // transition resets a GPU, the reference merely re-reads the mode
-// register (/root/reference/main.py:523-529). Here the device must
-// additionally PROVE it executes correctly inside the TEE:
+// register. Here the device must additionally PROVE it executes
+// correctly inside the TEE. This file is the one translation unit the
+// build compiles; the device code lives next to it:
 //
-//   1. bf16 MFMA GEMMs  — mfma_gemm_bf16 (128x128 step-3 structure),
-//                         mfma_gemm_bf16_256 / _256w (256x256 8-phase
-//                         deep-pipelined, 16x16x32 / 32x32x16 shapes) —
-//                         HBM -> LDS-DMA -> VGPR -> MFMA -> HBM;
-//   2. fp8 MFMA GEMMs   — mfma_gemm_fp8_128 / _256: MX-scaled OCP e4m3
-//                         (v_mfma_scale_*_f8f6f4, unit e8m0 scales);
-//   3. ref_gemm_f32     — plain VALU fp32 GEMM of the same inputs: the
-//                         independent on-device ground truth (inputs are
-//                         small integers, so the bf16 AND fp8 MFMA paths
-//                         must both agree BITWISE — any mismatch is
-//                         silicon/TEE trouble);
-//   4. lds_probe        — LDS cell sweep with rotating patterns;
-//   5. hbm_probe        — vectorized streaming copy + checksum (HBM3E
-//                         path, reported as GB/s);
-//   6. xGMI peer visibility via hipDeviceCanAccessPeer.
+//   gemm_common.hip    types, LDS swizzles, shared staging / epilogue /
+//                      remap helpers;
+//   gemm_bf16.hip      bf16 MFMA GEMMs: mfma_gemm_bf16 (128x128 step-3),
+//                      _256 / _256w (256x256 8-phase deep-pipelined,
+//                      16x16x32 / 32x32x16 ops), _128u (4 blocks/CU);
+//   gemm_fp8.hip       MX-scaled OCP e4m3 MFMA GEMMs (unit e8m0 scales):
+//                      mfma_gemm_fp8_128 / _256 / _128w / _128s / _128t /
+//                      _128u / _256u / _128pc / _256x / _128sk;
+//   probe_kernels.hip  fills, ref_gemm_f32 (plain VALU fp32 GEMM of the
+//                      same inputs: the independent on-device ground
+//                      truth), max-diff, checksum, LDS, HBM, liveness.
 //
-// Layout notes (from the CDNA4 guides): wave = 64 lanes; for
-// v_mfma_f32_16x16x32_bf16 each lane carries 8 bf16 of A and B and 4
-// fp32 of C/D; A lane mapping row=l&15, k=(l>>4)*8+j; B (we require the
-// second operand TRANSPOSED, i.e. Bt[N][K], so its lane mapping is the
-// same as A's with col=l&15); C/D mapping col=l&15, row=(l>>4)*4+r.
-// LDS tile images carry a 3-bit XOR bank swizzle (see swz()) so
-// ds_read_b128 fragment reads are bank-conflict-free while the
-// global->LDS DMA stays lane-linear (swizzle rides the source address).
+// cc_attest_device runs five legs in order:
+//   1. probe_bf16  — production bf16 GEMM dispatch, timed, compared
+//                    with ref_gemm_f32 (inputs are small integers, so
+//                    the bf16 AND fp8 MFMA paths must both agree
+//                    BITWISE — any mismatch is silicon/TEE trouble) and
+//                    checksummed;
+//   2. probe_fp8   — production fp8 GEMM dispatch, same reference;
+//   3. probe_lds   — LDS cell sweep with rotating patterns;
+//   4. probe_hbm   — vectorized streaming copy (HBM3E path, GB/s);
+//   5. probe_xgmi  — for every sampled accessible peer: timed copies of
+//                    the result buffer across the link and a checksum
+//                    recomputed ON THE PEER.
 
 #include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
 
+#include <array>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
+
+#include "gemm_common.hip"
+#include "gemm_bf16.hip"
+#include "gemm_fp8.hip"
+#include "probe_kernels.hip"
 
 #define CC_CHECK(expr)                                                         \
   do {                                                                         \
@@ -48,1741 +54,206 @@
     }                                                                          \
   } while (0)
 
-using bf16 = __bf16;
-typedef __attribute__((ext_vector_type(8))) bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) float float4v;
-
-// ---------------------------------------------------------------------------
-// Tiling parameters: 128x128 block tile, 4 waves in a 2x2 grid, each wave
-// owns a 64x64 sub-tile = 4x4 MFMA tiles of 16x16, K staged in 32-deep
-// chunks through LDS (double-buffered).
-// ---------------------------------------------------------------------------
-constexpr int BM = 128;  // block tile rows
-constexpr int BN = 128;  // block tile cols
-constexpr int BK = 64;   // K chunk per LDS stage
-
-// ---------------------------------------------------------------------------
-// deterministic small-integer fill: values in {-2,-1,0,1}; products and
-// K<=8192 partial sums stay exact in fp32 AND in the MFMA accumulator,
-// so the MFMA and VALU paths must agree bitwise.
-// ---------------------------------------------------------------------------
-__global__ void fill_bf16_lcg(bf16* __restrict__ out, long n, uint32_t seed) {
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    uint32_t x = (uint32_t)i * 1103515245u + seed * 747796405u + 12345u;
-    x ^= x >> 16;
-    x *= 2654435769u;
-    int v = (int)((x >> 13) & 3u) - 2;  // {-2,-1,0,1}
-    out[i] = (bf16)(float)v;
-  }
-}
-
-// identical value sequence in OCP e4m3 (exact for {-2,-1,0,1}): lets
-// the fp8 MFMA path be verified BITWISE against the same fp32 VALU
-// reference the bf16 path uses.
-__global__ void fill_fp8_lcg(unsigned char* __restrict__ out, long n,
-                             uint32_t seed) {
-  const unsigned char enc[4] = {0xC0, 0xB8, 0x00, 0x38};  // -2,-1,0,1
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n; i += stride) {
-    uint32_t x = (uint32_t)i * 1103515245u + seed * 747796405u + 12345u;
-    x ^= x >> 16;
-    x *= 2654435769u;
-    out[i] = enc[(x >> 13) & 3u];
-  }
-}
-
-// ---------------------------------------------------------------------------
-// MFMA bf16 GEMM:  C[M,N] = A[M,K] @ Bt[N,K]^T      (all row-major)
-// Grid: (N/BN, M/BM); block: 256 threads (4 waves, 2x2 of 64x64).
-//
-// Structure: the "step-3" ladder shape of the CDNA4 guide — 128x128
-// tile, BK=64, direct global->LDS DMA (global_load_lds_dwordx4, the
-// compiler never auto-emits it) double-buffered, st_16x32 XOR swizzle
-// applied on the pre-swizzled GLOBAL source address (glds lands
-// lane-linear in LDS, so the swizzle must ride the source) and on the
-// ds_read fragment address, which turns the 8-way ds_read_b128 bank
-// conflict of a linear [128][64]-bf16 image into a conflict-free read.
-// ---------------------------------------------------------------------------
-constexpr int TILE_B = BM * BK * 2;  // 16 KiB per operand tile
-
-__device__ __forceinline__ int swz(int byte_off) {
-  // 3-bit XOR swizzle: inject row bits 1-3 (byte bits 8-10 of the
-  // 128-B-row image) into bank bits 2-4 (byte bits 4-6). With the
-  // fragment pattern row=(lane&15|31), khalf=(lane>>4|5)*16B this puts
-  // the 16 lanes of every ds_read_b128 lane group on 16 distinct
-  // 4-bank quads (enumerated for all four groups) — the 1-bit st_16x32
-  // form left rows 0-3 on two quads (2-way conflict, ~9% of cycles in
-  // the PMC profile, profiles/v256_8192_pmc.txt).
-  return byte_off ^ (((byte_off >> 8) & 7) << 4);
-}
-
-__device__ __forceinline__ void stage_tile_glds(
-    const char* gbase, long row_stride_b, long k0_b, char* lds_tile,
-    int wave, int lane) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    int base = (wave * 4 + p) * 1024;       // wave-uniform LDS dest
-    int logical = swz(base + lane * 16);    // where lane's 16 B lands
-    int row = logical >> 7;                 // 128 B per logical row (BK=64)
-    int colb = logical & 127;
-    const char* g = gbase + (long)row * row_stride_b + k0_b + colb;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)g,
-        (__attribute__((address_space(3))) void*)(lds_tile + base), 16, 0, 0);
-  }
-}
-
-__global__ __launch_bounds__(256, 2) void mfma_gemm_bf16(
-    const bf16* __restrict__ A, const bf16* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K) {
-  // [buf][A|B][16 KiB]: one __shared__ object (a second one makes the
-  // compiler drain vmcnt before every ds_read of a glds pipeline).
-  __shared__ char lds[2 * 2 * TILE_B];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;            // 0..3
-  const int wave_m = (wave >> 1) * 64;  // wave row offset in block tile
-  const int wave_n = (wave & 1) * 64;   // wave col offset
-  const int block_m = blockIdx.y * BM;
-  const int block_n = blockIdx.x * BN;
-
-  const char* gA = (const char*)(A + (long)block_m * K);
-  const char* gB = (const char*)(Bt + (long)block_n * K);
-  const long row_b = (long)K * 2;
-
-  f32x4 acc[4][4] = {};  // 4x4 MFMA tiles of 16x16 per wave
-
-  const int lane15 = lane & 15;
-  const int khalf_b = (lane >> 4) * 16;  // fragment k byte offset
-
-  const int nk = K / BK;
-  // prologue: stage tile 0 into buffer 0
-  stage_tile_glds(gA, row_b, 0, &lds[0], wave, lane);
-  stage_tile_glds(gB, row_b, 0, &lds[TILE_B], wave, lane);
-  __syncthreads();  // drains the glds (vmcnt0 inside the barrier)
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    char* As = &lds[buf * 2 * TILE_B];
-    char* Bs = As + TILE_B;
-    // issue DMA for the NEXT tile into the other buffer (no wait here)
-    if (kt + 1 < nk) {
-      char* An = &lds[(buf ^ 1) * 2 * TILE_B];
-      stage_tile_glds(gA, row_b, (long)(kt + 1) * BK * 2, An, wave, lane);
-      stage_tile_glds(gB, row_b, (long)(kt + 1) * BK * 2, An + TILE_B, wave, lane);
-    }
-    // ---- MFMA over the 64-deep chunk: 2 k-steps of 32 ---------------
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      bf16x8 afrag[4], bfrag[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        int a_log = (wave_m + t * 16 + lane15) * 128 + ks * 64 + khalf_b;
-        int b_log = (wave_n + t * 16 + lane15) * 128 + ks * 64 + khalf_b;
-        afrag[t] = *(const bf16x8*)(As + swz(a_log));
-        bfrag[t] = *(const bf16x8*)(Bs + swz(b_log));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0);
-    }
-    // one barrier per K-tile: everyone done reading buf, and the
-    // in-flight glds for buf^1 is drained (implicit vmcnt(0) — the
-    // structural cost of the 2-barrier structure, accepted here).
-    __syncthreads();
-  }
-
-  // ---- epilogue: C/D mapping col=lane&15, row=(lane>>4)*4+r ----------
-  const int c_col = lane & 15;
-  const int c_row0 = (lane >> 4) * 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = block_m + wave_m + i * 16 + c_row0 + r;
-        int col = block_n + wave_n + j * 16 + c_col;
-        C[(long)row * N + col] = acc[i][j][r];
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// 256x256 8-phase deep-pipelined MFMA GEMM (the CDNA4 guide's 256²
-// template class). 512 threads = 8 waves (2M x 4N), BK=64, 128 KiB LDS:
-// per double-buffer slot one K-tile of A and B, each in two 16 KiB
-// halves (A rows 0-127 / 128-255; Bt rows likewise). Each phase
-// computes one 128x128 block-quadrant (mh,nh) x K=64 — per wave 16
-// MFMA — touching ONLY A-half mh and B-half nh, so half-tile slots free
-// progressively and one half-tile is prefetched per phase with raw
-// s_barrier + counted s_waitcnt vmcnt (never vmcnt(0) mid-loop except
-// the final two iterations, where prefetch guards would otherwise leave
-// needed DMAs undrained).
-//
-// Phase schedule per iteration J (t = 2J; quadrant order A0B0, A0B1,
-// A1B1, A1B0 for tile t in buf0 then tile t+1 in buf1; A fragments are
-// register-reused by quadrant pairs and B1 by phases 2-3, so the LDS
-// read phases per slot are: A0@p1, B0@p1+p4, B1@p2, A1@p3 — slots free
-// progressively and each phase prefetches exactly the slot freed the
-// phase before):
-//   p1 t:A0B0, prefetch B0(t+1);  p2 t:A0B1, A0(t+2);
-//   p3 t:A1B1, B1(t+2);           p4 t:A1B0, A1(t+2) + vmcnt(6);
-//   p5 t+1:A0B0, B0(t+2);         p6 t+1:A0B1, A0(t+3);
-//   p7 t+1:A1B1, B1(t+3);         p8 t+1:A1B0, A1(t+3) + vmcnt(6).
-// At each vmcnt(6)+s_barrier the three newest half-tiles may still fly;
-// everything a following phase reads is >= 3 phases old and therefore
-// drained for EVERY wave (the barrier makes the per-wave vmcnt
-// chip-wide). Race-screened bitwise on integer data and against torch
-// fp32 (tests/test_gpu_attest.py).
-// ---------------------------------------------------------------------------
-constexpr int BM2 = 256, BN2 = 256, BK2 = 64;
-constexpr int HALF_B = 16384;  // one half-tile (128 rows x 128 B)
-
-__device__ __forceinline__ char* slot_ptr(char* lds, int op, int buf, int half) {
-  return lds + ((op * 2 + buf) * 2 + half) * HALF_B;
-}
-
-// Stage one 16 KiB half-tile with 8 waves x 2 glds (1 KiB per wave per
-// instruction); st_16x32 swizzle rides the global source address.
-__device__ __forceinline__ void stage_half_glds(
-    const char* gbase, long row_stride_b, long k0_b, int row0,
-    char* lds_half, int wave, int lane) {
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    int base = (p * 8 + wave) * 1024;
-    int logical = swz(base + lane * 16);
-    int row = logical >> 7;
-    int colb = logical & 127;
-    const char* g = gbase + (long)(row0 + row) * row_stride_b + k0_b + colb;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)g,
-        (__attribute__((address_space(3))) void*)(lds_half + base), 16, 0, 0);
-  }
-}
-
-// Experiment toggles (A/B builds; default off):
-//   CC_EXP_PREFETCH_FIRST — issue the half-tile DMA before the phase's
-//     ds_reads (DMA in flight during LDS reads);
-//   CC_EXP_LGKM — partial s_waitcnt lgkmcnt(4) before the barrier so
-//     waves arrive with most reads drained (the template's optional
-//     pre-wait on 12-read phases).
-#ifndef CC_EXP_PREFETCH_FIRST
-#define CC_EXP_PREFETCH_FIRST 0
-#endif
-#ifndef CC_EXP_LGKM
-#define CC_EXP_LGKM 0
-#endif
-
-// one phase: ds-read only the fragments this quadrant does NOT already
-// hold (adjacent phases share an A-half or a B-half of the same K-tile,
-// so those fragments persist in VGPRs across the phase barrier: phases
-// read 12/4/8/4 b128 instead of 12 each), issue one half-tile prefetch,
-// raw barrier, lgkmcnt(0), 16 MFMA at prio 1, raw barrier.
-#define PHASE(buf, mh, nh, LOAD_A, LOAD_B, ACC, PREFETCH_STMT, DRAIN)          \
+// propagate a nonzero int status
+#define CC_TRY(expr)                                                           \
   do {                                                                         \
-    if (CC_EXP_PREFETCH_FIRST) {                                               \
-      PREFETCH_STMT;                                                           \
-    }                                                                          \
-    if (LOAD_A) {                                                              \
-      char* Ah = slot_ptr(lds, 0, (buf), (mh));                                \
-      _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                         \
-          _Pragma("unroll") for (int i = 0; i < 4; ++i) {                      \
-        int lg = (wave_mq + i * 16 + lane15) * 128 + ks * 64 + khalf_b;        \
-        af[i][ks] = *(const bf16x8*)(Ah + swz(lg));                            \
-      }                                                                        \
-    }                                                                          \
-    if (LOAD_B) {                                                              \
-      char* Bh = slot_ptr(lds, 1, (buf), (nh));                                \
-      _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                         \
-          _Pragma("unroll") for (int j = 0; j < 2; ++j) {                      \
-        int lg = (wave_nq + j * 16 + lane15) * 128 + ks * 64 + khalf_b;        \
-        bf[j][ks] = *(const bf16x8*)(Bh + swz(lg));                            \
-      }                                                                        \
-    }                                                                          \
-    if (!CC_EXP_PREFETCH_FIRST) {                                              \
-      PREFETCH_STMT;                                                           \
-    }                                                                          \
-    DRAIN;                                                                     \
-    if (CC_EXP_LGKM && ((LOAD_A) + (LOAD_B)) > 1)                              \
-      asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");                       \
-    __builtin_amdgcn_s_barrier();                                              \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                         \
-    __builtin_amdgcn_s_setprio(1);                                             \
-    _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                           \
-        _Pragma("unroll") for (int i = 0; i < 4; ++i)                          \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j)                          \
-            ACC[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(               \
-                af[i][ks], bf[j][ks], ACC[i][j], 0, 0, 0);                     \
-    __builtin_amdgcn_s_setprio(0);                                             \
-    __builtin_amdgcn_s_barrier();                                              \
+    int _rc = (expr);                                                          \
+    if (_rc != 0) return _rc;                                                  \
   } while (0)
 
-__global__ __launch_bounds__(512, 1) void mfma_gemm_bf16_256(
-    const bf16* __restrict__ A, const bf16* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K, int xcd_swizzle) {
-  __shared__ char lds[8 * HALF_B];  // 128 KiB, ONE shared object
+// ===========================================================================
+// Variant tables and dispatch
+// ===========================================================================
+// A launcher starts one kernel on the null stream (no sync); `arg` is
+// the kernel's extra opts / xcd_swizzle argument where it has one.
+typedef int (*GemmLauncher)(dim3 grid, int threads, const void* A,
+                            const void* Bt, void* C, int M, int N, int K,
+                            int arg);
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;               // 0..7
-  const int wave_mq = (wave >> 2) * 64;    // row offset inside a quadrant
-  const int wave_nq = (wave & 3) * 32;     // col offset inside a quadrant
-  const int lane15 = lane & 15;
-  const int khalf_b = (lane >> 4) * 16;
-  // XCD-aware bijective remap (dispatcher places block b on XCD b%8):
-  // consecutive remapped ids share an XCD's L2 -> tile locality when
-  // HBM-bound; host enables it only when the working set exceeds L3.
-  int wg = blockIdx.y * gridDim.x + blockIdx.x;
-  if (xcd_swizzle) {
-    int nwg = gridDim.x * gridDim.y;
-    int q = nwg >> 3, r = nwg & 7;
-    int xcd = wg & 7, o = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + o;
-  }
-  const int block_m = (wg / gridDim.x) * BM2;
-  const int block_n = (wg % gridDim.x) * BN2;
-
-  const char* gA = (const char*)(A + (long)block_m * K);
-  const char* gB = (const char*)(Bt + (long)block_n * K);
-  const long row_b = (long)K * 2;
-  const int nk = K / BK2;
-
-  // acc[mh][nh][i][j]: 2x2 quadrants x (4 m-frag x 2 n-frag) = 128 VGPR
-  f32x4 acc00[4][2] = {}, acc01[4][2] = {}, acc10[4][2] = {}, acc11[4][2] = {};
-  // fragment registers persist across phases (A shared by quadrant
-  // pairs (mh,0)/(mh,1); B1 shared by phases 2-3, same K-tile)
-  bf16x8 af[4][2], bf[2][2];
-
-#define STAGE(op, buf, half, tile)                                             \
-  stage_half_glds((op) == 0 ? gA : gB, row_b, (long)(tile) * BK2 * 2,          \
-                  (half) * 128, slot_ptr(lds, (op), (buf), (half)), wave, lane)
-
-  // prologue: tile 0 complete + A0,B1,A1 of tile 1 (iteration 0 stages
-  // only B0(1) itself, at p1); full drain once.
-  STAGE(0, 0, 0, 0);
-  STAGE(1, 0, 0, 0);
-  STAGE(0, 0, 1, 0);
-  STAGE(1, 0, 1, 0);
-  STAGE(0, 1, 0, 1);
-  STAGE(1, 1, 1, 1);
-  STAGE(0, 1, 1, 1);
-  __syncthreads();
-
-#define VM_DRAIN                                                               \
-  do {                                                                         \
-    if (tp + 4 >= nk)                                                          \
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                         \
-    else                                                                       \
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                         \
-  } while (0)
-
-  for (int tp = 0; tp < nk; tp += 2) {
-    // tile tp from buf0 (reads: 12 / 4 / 8 / 4 ds_read_b128) -----------
-    PHASE(0, 0, 0, 1, 1, acc00, if (tp + 1 < nk) STAGE(1, 1, 0, tp + 1), );
-    PHASE(0, 0, 1, 0, 1, acc01, if (tp + 2 < nk) STAGE(0, 0, 0, tp + 2), );
-    PHASE(0, 1, 1, 1, 0, acc11, if (tp + 2 < nk) STAGE(1, 0, 1, tp + 2), );
-    PHASE(0, 1, 0, 0, 1, acc10, if (tp + 2 < nk) STAGE(0, 0, 1, tp + 2), VM_DRAIN);
-    // tile tp+1 from buf1 ----------------------------------------------
-    PHASE(1, 0, 0, 1, 1, acc00, if (tp + 2 < nk) STAGE(1, 0, 0, tp + 2), );
-    PHASE(1, 0, 1, 0, 1, acc01, if (tp + 3 < nk) STAGE(0, 1, 0, tp + 3), );
-    PHASE(1, 1, 1, 1, 0, acc11, if (tp + 3 < nk) STAGE(1, 1, 1, tp + 3), );
-    PHASE(1, 1, 0, 0, 1, acc10, if (tp + 3 < nk) STAGE(0, 1, 1, tp + 3), VM_DRAIN);
-  }
-#undef VM_DRAIN
-#undef STAGE
-
-  // epilogue: C/D mapping col=lane&15, row=(lane>>4)*4+r
-  const int c_col = lane & 15;
-  const int c_row0 = (lane >> 4) * 4;
-#pragma unroll
-  for (int mh = 0; mh < 2; ++mh) {
-#pragma unroll
-    for (int nh = 0; nh < 2; ++nh) {
-      f32x4(*acc)[2] = mh == 0 ? (nh == 0 ? acc00 : acc01)
-                               : (nh == 0 ? acc10 : acc11);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            int row = block_m + mh * 128 + wave_mq + i * 16 + c_row0 + r;
-            int col = block_n + nh * 128 + wave_nq + j * 16 + c_col;
-            C[(long)row * N + col] = acc[i][j][r];
-          }
-        }
-      }
-    }
-  }
+template <typename T, void (*KERNEL)(const T*, const T*, float*, int, int, int)>
+static int launch_plain(dim3 grid, int threads, const void* A, const void* Bt,
+                        void* C, int M, int N, int K, int) {
+  hipLaunchKernelGGL(KERNEL, grid, dim3(threads), 0, 0, (const T*)A,
+                     (const T*)Bt, (float*)C, M, N, K);
+  return 0;
 }
 
-// ---------------------------------------------------------------------------
-// Same 8-phase 256x256 structure on v_mfma_f32_32x32x16_bf16 (the
-// higher-ceiling MFMA shape: 2382 vs 2075 TF/s µbench). Per quadrant a
-// wave computes 2 m-tiles of 32x32 over 4 k-steps of 16 (8 MFMA/phase).
-// Fragment maps: A row=l&31, k=(l>>5)*8+j; Bt col=l&31 likewise;
-// C/D col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5).
-// ---------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-#define PHASE32(buf, mh, nh, ACC, PREFETCH_STMT, DRAIN, LOAD_A, LOAD_B)        \
-  do {                                                                         \
-    if (LOAD_A) {                                                              \
-      char* Ah = slot_ptr(lds, 0, (buf), (mh));                                \
-      _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                         \
-          _Pragma("unroll") for (int t = 0; t < 2; ++t) {                      \
-        int lg = (wave_mq + t * 32 + lane31) * 128 + ks * 32 + khalf32_b;      \
-        a2[t][ks] = *(const bf16x8*)(Ah + swz(lg));                            \
-      }                                                                        \
-    }                                                                          \
-    if (LOAD_B) {                                                              \
-      char* Bh = slot_ptr(lds, 1, (buf), (nh));                                \
-      _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                       \
-        int lg = (wave_nq + lane31) * 128 + ks * 32 + khalf32_b;               \
-        b2[ks] = *(const bf16x8*)(Bh + swz(lg));                               \
-      }                                                                        \
-    }                                                                          \
-    PREFETCH_STMT;                                                             \
-    DRAIN;                                                                     \
-    __builtin_amdgcn_s_barrier();                                              \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                         \
-    __builtin_amdgcn_s_setprio(1);                                             \
-    _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                           \
-        _Pragma("unroll") for (int t = 0; t < 2; ++t)                          \
-            ACC[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(                  \
-                a2[t][ks], b2[ks], ACC[t], 0, 0, 0);                           \
-    __builtin_amdgcn_s_setprio(0);                                             \
-    __builtin_amdgcn_s_barrier();                                              \
-  } while (0)
-
-__global__ __launch_bounds__(512, 1) void mfma_gemm_bf16_256w(
-    const bf16* __restrict__ A, const bf16* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K, int xcd_swizzle) {
-  __shared__ char lds[8 * HALF_B];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wave_mq = (wave >> 2) * 64;
-  const int wave_nq = (wave & 3) * 32;
-  const int lane31 = lane & 31;
-  const int khalf32_b = (lane >> 5) * 16;
-  int wg = blockIdx.y * gridDim.x + blockIdx.x;
-  if (xcd_swizzle) {
-    int nwg = gridDim.x * gridDim.y;
-    int q = nwg >> 3, r = nwg & 7;
-    int xcd = wg & 7, o = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + o;
-  }
-  const int block_m = (wg / gridDim.x) * BM2;
-  const int block_n = (wg % gridDim.x) * BN2;
-
-  const char* gA = (const char*)(A + (long)block_m * K);
-  const char* gB = (const char*)(Bt + (long)block_n * K);
-  const long row_b = (long)K * 2;
-  const int nk = K / BK2;
-
-  f32x16 acc00[2] = {}, acc01[2] = {}, acc10[2] = {}, acc11[2] = {};
-  bf16x8 a2[2][4], b2[4];
-
-#define STAGE(op, buf, half, tile)                                             \
-  stage_half_glds((op) == 0 ? gA : gB, row_b, (long)(tile) * BK2 * 2,          \
-                  (half) * 128, slot_ptr(lds, (op), (buf), (half)), wave, lane)
-
-  STAGE(0, 0, 0, 0);
-  STAGE(1, 0, 0, 0);
-  STAGE(0, 0, 1, 0);
-  STAGE(1, 0, 1, 0);
-  STAGE(0, 1, 0, 1);
-  STAGE(1, 1, 1, 1);
-  STAGE(0, 1, 1, 1);
-  __syncthreads();
-
-#define VM_DRAIN                                                               \
-  do {                                                                         \
-    if (tp + 4 >= nk)                                                          \
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                         \
-    else                                                                       \
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                         \
-  } while (0)
-
-  for (int tp = 0; tp < nk; tp += 2) {
-    PHASE32(0, 0, 0, acc00, if (tp + 1 < nk) STAGE(1, 1, 0, tp + 1), , 1, 1);
-    PHASE32(0, 0, 1, acc01, if (tp + 2 < nk) STAGE(0, 0, 0, tp + 2), , 0, 1);
-    PHASE32(0, 1, 1, acc11, if (tp + 2 < nk) STAGE(1, 0, 1, tp + 2), , 1, 0);
-    PHASE32(0, 1, 0, acc10, if (tp + 2 < nk) STAGE(0, 0, 1, tp + 2), VM_DRAIN, 0, 1);
-    PHASE32(1, 0, 0, acc00, if (tp + 2 < nk) STAGE(1, 0, 0, tp + 2), , 1, 1);
-    PHASE32(1, 0, 1, acc01, if (tp + 3 < nk) STAGE(0, 1, 0, tp + 3), , 0, 1);
-    PHASE32(1, 1, 1, acc11, if (tp + 3 < nk) STAGE(1, 1, 1, tp + 3), , 1, 0);
-    PHASE32(1, 1, 0, acc10, if (tp + 3 < nk) STAGE(0, 1, 1, tp + 3), VM_DRAIN, 0, 1);
-  }
-#undef VM_DRAIN
-#undef STAGE
-
-  // epilogue: C/D col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5)
-  const int c_col32 = lane & 31;
-  const int c_rowhi = (lane >> 5) * 4;
-#pragma unroll
-  for (int mh = 0; mh < 2; ++mh) {
-#pragma unroll
-    for (int nh = 0; nh < 2; ++nh) {
-      f32x16* accq = mh == 0 ? (nh == 0 ? acc00 : acc01)
-                             : (nh == 0 ? acc10 : acc11);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          int row = block_m + mh * 128 + wave_mq + t * 32 + (reg & 3) +
-                    8 * (reg >> 2) + c_rowhi;
-          int col = block_n + nh * 128 + wave_nq + c_col32;
-          C[(long)row * N + col] = accq[t][reg];
-        }
-      }
-    }
-  }
+template <typename T,
+          void (*KERNEL)(const T*, const T*, float*, int, int, int, int)>
+static int launch_arg(dim3 grid, int threads, const void* A, const void* Bt,
+                      void* C, int M, int N, int K, int arg) {
+  hipLaunchKernelGGL(KERNEL, grid, dim3(threads), 0, 0, (const T*)A,
+                     (const T*)Bt, (float*)C, M, N, K, arg);
+  return 0;
 }
 
-// ---------------------------------------------------------------------------
-// MX-scaled fp8 (OCP e4m3) GEMM on the same 8-phase 256x256 structure:
-// v_mfma_scale_f32_32x32x64_f8f6f4 with unit e8m0 scales — the only
-// path to the ~5 PF fp8 rate on gfx950 (non-scaled fp8 MFMA runs at
-// the bf16 rate). BK = 128 fp8 elements = the same 128-B row image and
-// 16 KiB half-tiles as the bf16 template, so the phase schedule,
-// prefetch map, vmcnt drains and bank swizzle carry over unchanged.
-// Per phase a wave runs 4 MFMA (2 m-tiles x 2 k-steps of 64).
-// Fragment map: A row=l&31, k=(l>>5)*32+j (32 consecutive fp8 = two
-// ds_read_b128); Bt col=l&31 likewise; C/D layout is shape-determined
-// (same as 32x32 bf16).
-// ---------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(8))) int v8i;
-typedef __attribute__((ext_vector_type(4))) int v4i;
-
-constexpr int BK8 = 128;                 // fp8 elements per K-tile
-constexpr unsigned SCALE_ONE = 0x7F7F7F7Fu;  // e8m0 bias-127 = 2^0 per byte
-
-// fp8 swizzle: XOR only byte bits 5-6 so every 32-B fragment stays
-// physically contiguous — the fragment can then be ONE v8i load into a
-// contiguous 8-register tuple (assembling it from two 16-B halves
-// leaves the allocator building 8-tuples out of scattered pairs, which
-// fragments past 256 VGPRs and spills). Costs a few 2-way LDS bank
-// conflicts; fp8's read count is half bf16's, so that is cheap.
-__device__ __forceinline__ int swz8(int byte_off) {
-  return byte_off ^ (((byte_off >> 8) & 3) << 5);
+// forced split-K (the tiny-grid shape at any size): slice K so the grid
+// reaches ~1024 blocks, zero C, accumulate with atomics
+static int launch_splitk(dim3 grid, int threads, const void* A, const void* Bt,
+                         void* C, int M, int N, int K, int) {
+  int nk = K / BK8;
+  long blocks = (long)grid.x * grid.y;
+  int S = (int)(1024 / (blocks ? blocks : 1));
+  if (S > nk) S = nk;
+  if (S < 2) S = 2;
+  if (hipMemsetAsync(C, 0, (long)M * N * sizeof(float), 0) != hipSuccess)
+    return -4;
+  dim3 g(grid.x, grid.y, S);
+  hipLaunchKernelGGL(mfma_gemm_fp8_128sk, g, dim3(threads), 0, 0,
+                     (const char*)A, (const char*)Bt, (float*)C, M, N, K);
+  return 0;
 }
 
-__device__ __forceinline__ v8i load_frag32(const char* p) {
-  return *(const v8i*)(p);
+constexpr int kXcdAuto = -1;  // arg: XCD remap iff past_infinity_cache()
+
+struct GemmVariant {
+  int tile_m, tile_n;  // block tile; M and N must be multiples
+  int k_mult;          // K must be a multiple
+  int threads;
+  GemmLauncher launch;
+  int arg;
+};
+
+// bf16 variants, indexed by `which` of cc_mfma_gemm_bf16_variant:
+// 0 = 128x128 step-3, 1 = 256x256 8-phase (16x16 op),
+// 2 = 256x256 8-phase (32x32 op), 3 = 128x128 single-buffered
+// 4-blocks/CU (measured slower than the deep pipeline — kept as the
+// recorded negative arm of the occupancy series, BASELINE.md).
+static const GemmVariant kBf16Variants[] = {
+    {BM, BN, BK, 256, launch_plain<bf16, mfma_gemm_bf16>, 0},
+    {BM2, BN2, 2 * BK2, 512, launch_arg<bf16, mfma_gemm_bf16_256>, kXcdAuto},
+    {BM2, BN2, 2 * BK2, 512, launch_arg<bf16, mfma_gemm_bf16_256w>, kXcdAuto},
+    {BM, BN, 64, 256, launch_plain<bf16, mfma_gemm_bf16_128u>, 0},
+};
+enum { kBf16_128 = 0, kBf16_256 = 1, kBf16_256w = 2 };
+
+// fp8 variants, indexed by `which` of cc_mfma_gemm_fp8_variant
+// (measured ladder in BASELINE.md):
+//  0 = 128-tile BK=128 double-buffered (2 blocks/CU),
+//  1 = 256-tile 8-phase deep pipeline,
+//  2 = 128-tile BK=256 (1 block/CU),
+//  3 = BK=64 32x32-op (4 blocks/CU; production's K%64-only fall-back),
+//  4 = BK=128 1.5-buffered (3 blocks/CU),
+//  5 = BK=128 SINGLE-buffered (4 blocks/CU; production past 1 block/CU),
+//  6 = 256x128 tile, 512 threads (2 blocks/CU),
+//  7 = producer/consumer wave split (4 stage waves + 4 MFMA waves,
+//      LDS-flag handoff, no block barrier in the K loop; production at
+//      <=1 block/CU),
+//  8 = variant 5 + XCD remap, 9 = variant 7 + XCD remap,
+//  10 = variant 5 + timing skew, 11 = + kt rotation, 12 = skew + rotation,
+//  13 = 256x256 @ 1 block/CU, persistent fragments, full double buffer,
+//  14 = split-K of variant 5 (hw fp32 atomics into a zeroed C).
+static const GemmVariant kFp8Variants[] = {
+    {BM, BN, BK8, 256, launch_plain<char, mfma_gemm_fp8_128>, 0},
+    {BM2, BN2, 2 * BK8, 512, launch_arg<char, mfma_gemm_fp8_256>, kXcdAuto},
+    {BM, BN, BK8L, 256, launch_plain<char, mfma_gemm_fp8_128w>, 0},
+    {BM, BN, 64, 256, launch_plain<char, mfma_gemm_fp8_128s>, 0},
+    {BM, BN, BK8, 256, launch_plain<char, mfma_gemm_fp8_128t>, 0},
+    {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 0},
+    {256, BN, BK8, 512, launch_plain<char, mfma_gemm_fp8_256u>, 0},
+    {BM, BN, BK8, 512, launch_arg<char, mfma_gemm_fp8_128pc>, 0},
+    {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 1},
+    {BM, BN, BK8, 512, launch_arg<char, mfma_gemm_fp8_128pc>, 1},
+    {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 2},
+    {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 4},
+    {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 6},
+    {256, 256, BK8, 512, launch_plain<char, mfma_gemm_fp8_256x>, 0},
+    {BM, BN, BK8, 256, launch_splitk, 0},
+};
+enum { kFp8_128s = 3, kFp8_128u = 5, kFp8_128pc = 7 };
+
+// working set (both operands + fp32 C) past the 256 MiB Infinity Cache:
+// the XCD remap is enabled only then
+static int past_infinity_cache(int M, int N, int K, int elem_bytes) {
+  long ws = (long)elem_bytes * K * (M + N) + 4L * M * N;
+  return ws > (256L << 20) ? 1 : 0;
 }
 
-// staging for the fp8 image: same lane-linear glds, swz8 on the source
-__device__ __forceinline__ void stage_half_glds8(
-    const char* gbase, long row_stride_b, long k0_b, int row0,
-    char* lds_half, int wave, int lane) {
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    int base = (p * 8 + wave) * 1024;
-    int logical = swz8(base + lane * 16);
-    int row = logical >> 7;
-    int colb = logical & 127;
-    const char* g = gbase + (long)(row0 + row) * row_stride_b + k0_b + colb;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)g,
-        (__attribute__((address_space(3))) void*)(lds_half + base), 16, 0, 0);
-  }
+static bool variant_fits(const GemmVariant& v, int M, int N, int K) {
+  return M % v.tile_m == 0 && N % v.tile_n == 0 && K % v.k_mult == 0;
 }
 
-// ALL fragments are transient: loaded INSIDE the prio section with
-// one-MFMA lifetimes (only the 128-VGPR accumulators persist). At
-// 32 B/lane fragments, persisting A/B across the barrier — the bf16
-// template's shape — fragments the allocator around the 10-operand
-// scaled MFMA and spills glds addressing temporaries to scratch
-// (624-1052 B/lane measured), destroying the pipeline. Post-barrier
-// reads are safe: the compiler's counted lgkmcnt before each MFMA use
-// retires every read before the wave's last MFMA, hence before the
-// phase's closing barrier; the slot's refill DMA only issues after
-// that barrier.
-
-// 4-pass variant of the swz8 staging (16 KiB tile staged by 4 waves)
-__device__ __forceinline__ void stage_tile_glds8x4(
-    const char* gbase, long row_stride_b, long k0_b, char* lds_tile,
-    int wave, int lane) {
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    int base = (wave * 4 + p) * 1024;
-    int logical = swz8(base + lane * 16);
-    int row = logical >> 7;
-    int colb = logical & 127;
-    const char* g = gbase + (long)row * row_stride_b + k0_b + colb;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)g,
-        (__attribute__((address_space(3))) void*)(lds_tile + base), 16, 0, 0);
-  }
+static long variant_blocks(const GemmVariant& v, int M, int N) {
+  return (long)(N / v.tile_n) * (M / v.tile_m);
 }
 
-// fp8 step-3 variant with BK=64 + the 32x32x64 op: 32 KiB LDS/block
-// -> 4 blocks/CU (16 waves/CU) — tests the occupancy hypothesis (the
-// BK=256 arm showed the limiter is latency hiding, not FLOP/byte).
-// Image rows are 64 B; swizzle injects row bit 2 into bank bit 3
-// (byte 5 — whole-fragment granularity, see the BK=256 lesson);
-// residual 4-way conflicts on rows mod 8 accepted for the experiment.
-__device__ __forceinline__ int swz64(int off) {
-  return off ^ (((off >> 8) & 1) << 5);
+// Launch one table entry (no sync); -2 for a shape that does not fit.
+static int launch_variant(const GemmVariant& v, const void* A, const void* Bt,
+                          void* C, int M, int N, int K, int arg) {
+  if (!variant_fits(v, M, N, K)) return -2;
+  dim3 grid(N / v.tile_n, M / v.tile_m);
+  return v.launch(grid, v.threads, A, Bt, C, M, N, K, arg);
 }
 
-__device__ __forceinline__ void stage_tile_glds8s(
-    const char* gbase, long row_stride_b, long k0_b, char* lds_tile,
-    int wave, int lane) {
-#pragma unroll
-  for (int p = 0; p < 2; ++p) {
-    int base = (wave * 2 + p) * 1024;
-    int logical = swz64(base + lane * 16);
-    int row = logical >> 6;  // 64 B per row
-    int colb = logical & 63;
-    const char* g = gbase + (long)row * row_stride_b + k0_b + colb;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)g,
-        (__attribute__((address_space(3))) void*)(lds_tile + base), 16, 0, 0);
-  }
+// Forced variant: table lookup (unknown `which` -> entry 0), launch, sync.
+static int run_forced_variant(const GemmVariant* table, int count,
+                              int elem_bytes, int device, const void* A,
+                              const void* Bt, void* C, int M, int N, int K,
+                              int which) {
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  const GemmVariant& v = table[which > 0 && which < count ? which : 0];
+  int arg =
+      v.arg == kXcdAuto ? past_infinity_cache(M, N, K, elem_bytes) : v.arg;
+  int rc = launch_variant(v, A, Bt, C, M, N, K, arg);
+  if (rc != 0) return rc;
+  return (int)hipDeviceSynchronize();
 }
 
-#define MFMA_FP8W_ASM(ACCX, AOP, BOP)                                         \
-  asm volatile(                                                               \
-      "v_mfma_scale_f32_32x32x64_f8f6f4 %0, %1, %2, %0, %3, %4 "              \
-      "op_sel_hi:[0,0,0]"                                                     \
-      : "+v"(ACCX)                                                            \
-      : "v"(AOP), "v"(BOP), "v"(sc_reg), "v"(sc_reg))
-
-__global__ __launch_bounds__(256, 4) void mfma_gemm_fp8_128s(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K) {
-  __shared__ char lds[2 * 2 * 8192];  // [buf][A|B][8 KiB]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wave_m = (wave >> 1) * 64;
-  const int wave_n = (wave & 1) * 64;
-  const int block_m = blockIdx.y * BM;
-  const int block_n = blockIdx.x * BN;
-
-  const char* gA = A + (long)block_m * K;
-  const char* gB = Bt + (long)block_n * K;
-  const long row_b = (long)K;
-
-  typedef __attribute__((ext_vector_type(16))) float f32x16v;
-  f32x16v acc[2][2] = {};  // 2x2 tiles of 32x32 per wave (64 VGPR)
-  const int lane31 = lane & 31;
-  const int kq_b = (lane >> 5) * 32;
-  int sc_reg;
-  asm("v_mov_b32 %0, 0x7f7f7f7f" : "=v"(sc_reg));
-
-  const int nk = K / 64;
-  stage_tile_glds8s(gA, row_b, 0, &lds[0], wave, lane);
-  stage_tile_glds8s(gB, row_b, 0, &lds[8192], wave, lane);
-  __syncthreads();
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    char* As = &lds[buf * 2 * 8192];
-    char* Bs = As + 8192;
-    if (kt + 1 < nk) {
-      char* An = &lds[(buf ^ 1) * 2 * 8192];
-      stage_tile_glds8s(gA, row_b, (long)(kt + 1) * 64, An, wave, lane);
-      stage_tile_glds8s(gB, row_b, (long)(kt + 1) * 64, An + 8192, wave, lane);
-    }
-    {
-      v8i afrag[2], bfrag[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        int la = (wave_m + i * 32 + lane31) * 64 + kq_b;
-        int lb = (wave_n + i * 32 + lane31) * 64 + kq_b;
-        afrag[i] = load_frag32(As + swz64(la));
-        bfrag[i] = load_frag32(Bs + swz64(lb));
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          MFMA_FP8W_ASM(acc[i][j], afrag[i], bfrag[j]);
-    }
-    __syncthreads();
+// Launch the best-fitting bf16 MFMA GEMM variant (no sync).
+static int launch_mfma_gemm(const void* A, const void* Bt, void* C, int M,
+                            int N, int K) {
+  const GemmVariant& v128 = kBf16Variants[kBf16_128];
+  const GemmVariant& v256 = kBf16Variants[kBf16_256];
+  // SMALL/MID sizes: the 128-tile step-3 kernel wins decisively below
+  // ~2048² output — 407 vs 252 TF @2048³, 64 vs 51 @1024³
+  // (profiles/final_kernel_sweep_r02.json): the deep 256-tile pipeline
+  // cannot fill its phase schedule on a 64-block grid. Rule: take the
+  // 128-tile shape whenever ITS grid still fits <=1 block/CU.
+  if (variant_fits(v128, M, N, K) && variant_blocks(v128, M, N) <= 256)
+    return launch_variant(v128, A, Bt, C, M, N, K, 0);
+  if (variant_fits(v256, M, N, K)) {
+    // enable the XCD remap only past the 256 MiB Infinity Cache
+    int swz_on = past_infinity_cache(M, N, K, 2);
+    // measured across boxes: the 32x32x16 shape wins at <=1 block/CU
+    // grids (935 vs 848 TF @4096^3), the 16x16x32 shape past that
+    // (1129 vs 1096 @8192^3) — profiles/gemm_final_sweep_2026-09-13.json
+    if (variant_blocks(v256, M, N) <= 256)
+      return launch_variant(kBf16Variants[kBf16_256w], A, Bt, C, M, N, K,
+                            swz_on);
+    return launch_variant(v256, A, Bt, C, M, N, K, swz_on);
   }
-  asm volatile("s_nop 15\ns_nop 15\ns_nop 2" :::);
-
-  // 32x32 C/D map: col=lane&31, row=(reg&3)+8*(reg>>2)+4*(lane>>5)
-  const int c_col32 = lane & 31;
-  const int c_rowhi = (lane >> 5) * 4;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        int row = block_m + wave_m + i * 32 + (reg & 3) + 8 * (reg >> 2) + c_rowhi;
-        int col = block_n + wave_n + j * 32 + c_col32;
-        C[(long)row * N + col] = acc[i][j][reg];
-      }
+  return launch_variant(v128, A, Bt, C, M, N, K, 0);
 }
 
-// fp8 BK=128 single-buffered at 4 blocks/CU: the remaining untried
-// corner of the (BK, blocks/CU) grid — same 32 KiB LDS as the BK=64
-// double-buffered shape (128s) but spent on tile DEPTH instead of a
-// second buffer: stage A+B serially, one sync, 2x the math per
-// barrier pair; the serial stage window is covered by the other 3
-// blocks on the CU. Uses the 32x32x64 asm op (acc 2x2xf32x16 = 64
-// VGPR) to stay under the 128-VGPR budget of 4 waves/SIMD.
-// opts bitfield: 1 = XCD remap (measured LOSS for this tile size,
-// fp8_ab_2 — kept for the record); 2 = timing skew (stagger
-// co-resident blocks' barrier cadence: PMC shows 43% of wave cycles
-// parked at 8192, consistent with the four blocks of a CU aligning
-// their stage windows so the MFMA pipe idles in lockstep); 4 = kt
-// rotation (same de-phasing applied to the DATA index — spreads tile
-// reads in time for L2).
-__global__ __launch_bounds__(256, 4) void mfma_gemm_fp8_128u(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K, int opts) {
-  __shared__ char lds[2 * 16384];  // [A][B], single-buffered
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wave_m = (wave >> 1) * 64;
-  const int wave_n = (wave & 1) * 64;
-  // XCD-aware bijective remap (same scheme as the 256-tile kernels):
-  // the dispatcher places block b on XCD b%8, so remap makes
-  // consecutive OUTPUT tiles co-resident in one XCD's L2 — A/B row
-  // reuse stops crossing dies once the working set exceeds the 256 MiB
-  // Infinity Cache (host enables it only then).
-  int wg = blockIdx.y * gridDim.x + blockIdx.x;
-  if (opts & 1) {
-    int nwg = gridDim.x * gridDim.y;
-    int q = nwg >> 3, r = nwg & 7;
-    int xcd = wg & 7, o = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + o;
+// Best-fitting fp8 launch (no sync). Measured dispatch policy:
+// - <=256 blocks (<=1 block/CU): producer/consumer wave split (stage
+//   windows fully exposed there; +16% measured, fp8_ab_1/boundary);
+// - past 1 block/CU: the single-buffered 4-blocks/CU barrier shape
+//   (occupancy wins; 2125 vs 1811 @8k).
+// Split-K for tiny grids was built and MEASURED OUT (fp8_sk.json:
+// 50.7 vs 111.5 TF @1024 — sub-2048 sizes are launch-latency bound,
+// not occupancy bound; the C memset + atomic RMW are pure overhead).
+// K%64-only shapes fall back to the BK=64 4-blocks/CU kernel.
+static int launch_fp8_best(const void* A, const void* Bt, void* C, int M,
+                           int N, int K) {
+  const GemmVariant& pc = kFp8Variants[kFp8_128pc];
+  if (variant_fits(pc, M, N, K)) {
+    int swz_on = past_infinity_cache(M, N, K, 1);
+    if (variant_blocks(pc, M, N) <= 256)
+      return launch_variant(pc, A, Bt, C, M, N, K, swz_on);
+    return launch_variant(kFp8Variants[kFp8_128u], A, Bt, C, M, N, K, swz_on);
   }
-  const int block_m = (wg / gridDim.x) * BM;
-  const int block_n = (wg % gridDim.x) * BN;
-  if (opts & 2) {
-    // de-phase the ~4 co-resident blocks of a CU: dispatch walks XCDs
-    // round-robin (block b -> XCD b%8), so blocks with consecutive
-    // (b>>3) land near each other — skew their start by quarters of
-    // the ~2 us per-kt round so stage windows interleave with the
-    // neighbors' MFMA windows instead of aligning.
-    int slot = (wg >> 3) & 3;
-    for (int s = 0; s < slot * 3; ++s) __builtin_amdgcn_s_sleep(8);
-  }
-
-  const char* gA = A + (long)block_m * K;
-  const char* gB = Bt + (long)block_n * K;
-  const long row_b = (long)K;
-
-  typedef __attribute__((ext_vector_type(16))) float f32x16v;
-  f32x16v acc[2][2] = {};
-  const int lane31 = lane & 31;
-  const int kq_b = (lane >> 5) * 32;
-  int sc_reg;
-  asm("v_mov_b32 %0, 0x7f7f7f7f" : "=v"(sc_reg));
-
-  char* As = &lds[0];
-  char* Bs = &lds[16384];
-  const int nk = K / BK8;
-  // fp32 accumulation over kt is order-independent for the bitwise
-  // integer screens; rotation only changes WHICH tile each block
-  // touches at a given time
-  const int kt0 = (opts & 4) ? ((wg >> 3) & 3) * (nk >> 2) : 0;
-  for (int ki = 0; ki < nk; ++ki) {
-    const int kt = kt0 ? (ki + kt0) % nk : ki;
-    stage_tile_glds8x4(gA, row_b, (long)kt * BK8, As, wave, lane);
-    stage_tile_glds8x4(gB, row_b, (long)kt * BK8, Bs, wave, lane);
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      v8i afrag[2], bfrag[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        int la = (wave_m + i * 32 + lane31) * 128 + ks * 64 + kq_b;
-        int lb = (wave_n + i * 32 + lane31) * 128 + ks * 64 + kq_b;
-        afrag[i] = load_frag32(As + swz8(la));
-        bfrag[i] = load_frag32(Bs + swz8(lb));
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          MFMA_FP8W_ASM(acc[i][j], afrag[i], bfrag[j]);
-    }
-    __syncthreads();
-  }
-  asm volatile("s_nop 15\ns_nop 15\ns_nop 2" :::);
-
-  const int c_col32 = lane & 31;
-  const int c_rowhi = (lane >> 5) * 4;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        int row = block_m + wave_m + i * 32 + (reg & 3) + 8 * (reg >> 2) + c_rowhi;
-        int col = block_n + wave_n + j * 32 + c_col32;
-        C[(long)row * N + col] = acc[i][j][reg];
-      }
-}
-
-// ---------------------------------------------------------------------------
-// fp8 producer/consumer wave split (the round-2 lever named by the
-// measured ladder): 512 threads = 4 PRODUCER waves (glds staging only)
-// + 4 CONSUMER waves (MFMA only), double-buffered 64 KiB LDS,
-// 2 blocks/CU -> 16 waves/CU (the winner's occupancy). There is NO
-// block barrier in the K loop: buffers hand off through LDS flag
-// counters (monotonic, so no reset races), producers run up to one
-// buffer ahead, and consumers never sit in a stage window — the
-// decoupling the barrier-stepped shapes cannot express. Safety: the
-// flag polls are iteration-bounded so a logic bug produces garbage
-// (caught by the bitwise screens), never a wedged GPU.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ bool lds_wait_ge(volatile int* p, int target) {
-  for (long spin = 0; *p < target; ++spin) {
-    if (spin > (1L << 24)) return false;  // bail, don't hang the device
-    __builtin_amdgcn_s_sleep(1);
-  }
-  return true;
-}
-
-__global__ __launch_bounds__(512, 2) void mfma_gemm_fp8_128pc(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K, int xcd_swizzle) {
-  __shared__ char lds[2 * 2 * 16384];  // [buf][A|B]
-  __shared__ int prod_ready[2];        // 4 per staged iteration on buf
-  __shared__ int cons_done[2];         // 4 per consumed iteration on buf
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;  // 0..7
-  int wg = blockIdx.y * gridDim.x + blockIdx.x;
-  if (xcd_swizzle) {
-    int nwg = gridDim.x * gridDim.y;
-    int q = nwg >> 3, r = nwg & 7;
-    int xcd = wg & 7, o = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + o;
-  }
-  const int block_m = (wg / gridDim.x) * BM;
-  const int block_n = (wg % gridDim.x) * BN;
-  const char* gA = A + (long)block_m * K;
-  const char* gB = Bt + (long)block_n * K;
-  const long row_b = (long)K;
-  const int nk = K / BK8;
-
-  if (tid < 2) {
-    prod_ready[tid] = 0;
-    cons_done[tid] = 0;
-  }
-  __syncthreads();  // the only block barrier
-
-  if (wave < 4) {
-    // ---- producer: stage iteration kt into buffer kt&1 --------------
-    for (int kt = 0; kt < nk; ++kt) {
-      const int b = kt & 1;
-      if (kt >= 2 && !lds_wait_ge(&cons_done[b], 4 * (kt / 2))) return;
-      char* As = &lds[b * 2 * 16384];
-      stage_tile_glds8x4(gA, row_b, (long)kt * BK8, As, wave, lane);
-      stage_tile_glds8x4(gB, row_b, (long)kt * BK8, As + 16384, wave, lane);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      if (lane == 0) atomicAdd(&prod_ready[b], 1);
-    }
-    return;
-  }
-
-  // ---- consumer: 64x64 per wave (same fragment map as the winner) ---
-  const int cw = wave - 4;
-  const int wave_m = (cw >> 1) * 64;
-  const int wave_n = (cw & 1) * 64;
-  typedef __attribute__((ext_vector_type(16))) float f32x16v;
-  f32x16v acc[2][2] = {};
-  const int lane31 = lane & 31;
-  const int kq_b = (lane >> 5) * 32;
-  int sc_reg;
-  asm("v_mov_b32 %0, 0x7f7f7f7f" : "=v"(sc_reg));
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const int b = kt & 1;
-    if (!lds_wait_ge(&prod_ready[b], 4 * (kt / 2 + 1))) return;
-    char* As = &lds[b * 2 * 16384];
-    char* Bs = As + 16384;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      v8i afrag[2], bfrag[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        int la = (wave_m + i * 32 + lane31) * 128 + ks * 64 + kq_b;
-        int lb = (wave_n + i * 32 + lane31) * 128 + ks * 64 + kq_b;
-        afrag[i] = load_frag32(As + swz8(la));
-        bfrag[i] = load_frag32(Bs + swz8(lb));
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          MFMA_FP8W_ASM(acc[i][j], afrag[i], bfrag[j]);
-    }
-    // every LDS read of this buffer must retire before releasing it
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (lane == 0) atomicAdd(&cons_done[b], 1);
-  }
-  asm volatile("s_nop 15\ns_nop 15\ns_nop 2" :::);
-
-  const int c_col32 = lane & 31;
-  const int c_rowhi = (lane >> 5) * 4;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        int row = block_m + wave_m + i * 32 + (reg & 3) + 8 * (reg >> 2) + c_rowhi;
-        int col = block_n + wave_n + j * 32 + c_col32;
-        C[(long)row * N + col] = acc[i][j][reg];
-      }
-}
-
-// ---------------------------------------------------------------------------
-// fp8 split-K for SMALL grids: at dim 1024 the 128-tile grid is 64
-// blocks on 256 CUs — 75% of the chip idles and the GEMM runs at ~2%
-// of peak. blockIdx.z slices the K loop; partial tiles accumulate
-// into C with hardware fp32 atomics (C is zeroed by the launcher).
-// Determinism note: accumulation ORDER varies run to run, but the
-// attestation ground truth is integer-valued fp32 (exact under any
-// order, magnitudes << 2^24), so the bitwise screens still hold;
-// random-data tests use tolerances as always.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 4) void mfma_gemm_fp8_128sk(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K) {
-  __shared__ char lds[2 * 16384];  // [A][B], single-buffered
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wave_m = (wave >> 1) * 64;
-  const int wave_n = (wave & 1) * 64;
-  const int block_m = blockIdx.y * BM;
-  const int block_n = blockIdx.x * BN;
-
-  const char* gA = A + (long)block_m * K;
-  const char* gB = Bt + (long)block_n * K;
-  const long row_b = (long)K;
-
-  typedef __attribute__((ext_vector_type(16))) float f32x16v;
-  f32x16v acc[2][2] = {};
-  const int lane31 = lane & 31;
-  const int kq_b = (lane >> 5) * 32;
-  int sc_reg;
-  asm("v_mov_b32 %0, 0x7f7f7f7f" : "=v"(sc_reg));
-
-  char* As = &lds[0];
-  char* Bs = &lds[16384];
-  const int nk = K / BK8;
-  // this slice's K range (last slice takes the remainder)
-  const int S = gridDim.z;
-  const int chunk = (nk + S - 1) / S;
-  const int kt0 = blockIdx.z * chunk;
-  const int kt1 = min(nk, kt0 + chunk);
-  for (int kt = kt0; kt < kt1; ++kt) {
-    stage_tile_glds8x4(gA, row_b, (long)kt * BK8, As, wave, lane);
-    stage_tile_glds8x4(gB, row_b, (long)kt * BK8, Bs, wave, lane);
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      v8i afrag[2], bfrag[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        int la = (wave_m + i * 32 + lane31) * 128 + ks * 64 + kq_b;
-        int lb = (wave_n + i * 32 + lane31) * 128 + ks * 64 + kq_b;
-        afrag[i] = load_frag32(As + swz8(la));
-        bfrag[i] = load_frag32(Bs + swz8(lb));
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          MFMA_FP8W_ASM(acc[i][j], afrag[i], bfrag[j]);
-    }
-    __syncthreads();
-  }
-  asm volatile("s_nop 15\ns_nop 15\ns_nop 2" :::);
-
-  const int c_col32 = lane & 31;
-  const int c_rowhi = (lane >> 5) * 4;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        int row = block_m + wave_m + i * 32 + (reg & 3) + 8 * (reg >> 2) + c_rowhi;
-        int col = block_n + wave_n + j * 32 + c_col32;
-        // hardware global fp32 atomic (gfx90a+): exact for the
-        // integer-valued ground truth regardless of arrival order
-        unsafeAtomicAdd(&C[(long)row * N + col], acc[i][j][reg]);
-      }
-}
-
-// ---------------------------------------------------------------------------
-// fp8 256x256 tile at ONE block/CU (round-2 design point the ladder
-// never tried): 512 threads = 8 waves = 2 waves/SIMD -> 256-VGPR
-// budget, so the 128-VGPR accumulator AND all six 32-B fragments per
-// ks persist in registers with no spills — the constraint that broke
-// the bf16-template fp8 256 kernel (transient frags, 1.46 PF). LDS is
-// a full double buffer (2 x 64 KiB); each kt overlaps the next tile's
-// DMA with 16 MFMAs/wave of math. FLOP/byte doubles vs the 128-tile
-// winner (256 vs 128), halving the L2 staging traffic that kernel
-// runs at (9.2 TB/s of 34.5). Risk: only 2 MFMA-issuing waves/SIMD —
-// the BK=256 lesson says 1/SIMD loses; 2/SIMD with 8 independent
-// accumulator chains per wave is the open question this measures.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(512, 1) void mfma_gemm_fp8_256x(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K) {
-  __shared__ char lds[2 * 2 * 32768];  // [buf][A|B], 128 KiB
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;            // 0..7
-  const int wave_m = (wave >> 1) * 64;  // 0..192
-  const int wave_n = (wave & 1) * 128;  // 0,128
-  const int block_m = blockIdx.y * 256;
-  const int block_n = blockIdx.x * 256;
-
-  const char* gA = A + (long)block_m * K;
-  const char* gB = Bt + (long)block_n * K;
-  const long row_b = (long)K;
-
-  typedef __attribute__((ext_vector_type(16))) float f32x16v;
-  f32x16v acc[2][4] = {};  // 2 m-tiles x 4 n-tiles of 32x32 = 128 VGPR
-  const int lane31 = lane & 31;
-  const int kq_b = (lane >> 5) * 32;
-  int sc_reg;
-  asm("v_mov_b32 %0, 0x7f7f7f7f" : "=v"(sc_reg));
-
-  const int nk = K / BK8;
-  // prologue: tile 0 into buffer 0 (8 waves x 4 KiB per 32 KiB tile)
-  stage_tile_glds8x4(gA, row_b, 0, &lds[0], wave, lane);
-  stage_tile_glds8x4(gB, row_b, 0, &lds[32768], wave, lane);
-  __syncthreads();
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    char* As = &lds[buf * 2 * 32768];
-    char* Bs = As + 32768;
-    if (kt + 1 < nk) {  // overlap next tile's DMA with this tile's math
-      char* An = &lds[(buf ^ 1) * 2 * 32768];
-      stage_tile_glds8x4(gA, row_b, (long)(kt + 1) * BK8, An, wave, lane);
-      stage_tile_glds8x4(gB, row_b, (long)(kt + 1) * BK8, An + 32768, wave,
-                         lane);
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      v8i afrag[2], bfrag[4];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        int la = (wave_m + i * 32 + lane31) * 128 + ks * 64 + kq_b;
-        afrag[i] = load_frag32(As + swz8(la));
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        int lb = (wave_n + j * 32 + lane31) * 128 + ks * 64 + kq_b;
-        bfrag[j] = load_frag32(Bs + swz8(lb));
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          MFMA_FP8W_ASM(acc[i][j], afrag[i], bfrag[j]);
-    }
-    // barrier drains the in-flight glds (vmcnt(0) inside) and fences
-    // every wave's reads of this buffer before its refill
-    __syncthreads();
-  }
-  asm volatile("s_nop 15\ns_nop 15\ns_nop 2" :::);
-
-  const int c_col32 = lane & 31;
-  const int c_rowhi = (lane >> 5) * 4;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        int row = block_m + wave_m + i * 32 + (reg & 3) + 8 * (reg >> 2) + c_rowhi;
-        int col = block_n + wave_n + j * 32 + c_col32;
-        C[(long)row * N + col] = acc[i][j][reg];
-      }
-}
-
-// fp8 256x128 tile at the winner's wave occupancy: 512 threads,
-// single-buffered 48 KiB LDS (A 32 KiB + B 16 KiB) -> 2 blocks/CU =
-// 16 waves/CU, same as the 128x128 winner, but 1.33x the FLOPs per
-// staged byte (A bytes amortized over twice the output rows). Tests
-// whether the stage window is DMA-rate-bound (this wins) or
-// latency-bound (occupancy already covers it; this ties or loses to
-// the coarser 8-wave barrier).
-__global__ __launch_bounds__(512, 2) void mfma_gemm_fp8_256u(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K) {
-  __shared__ char lds[3 * 16384];  // [A: 32 KiB][B: 16 KiB]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;  // 0..7
-  const int wave_m = (wave >> 1) * 64;  // 0..192
-  const int wave_n = (wave & 1) * 64;   // 0,64
-  const int block_m = blockIdx.y * 256;
-  const int block_n = blockIdx.x * BN;
-
-  const char* gA = A + (long)block_m * K;
-  const char* gB = Bt + (long)block_n * K;
-  const long row_b = (long)K;
-
-  typedef __attribute__((ext_vector_type(16))) float f32x16v;
-  f32x16v acc[2][2] = {};
-  const int lane31 = lane & 31;
-  const int kq_b = (lane >> 5) * 32;
-  int sc_reg;
-  asm("v_mov_b32 %0, 0x7f7f7f7f" : "=v"(sc_reg));
-
-  char* As = &lds[0];
-  char* Bs = &lds[32768];
-  const int nk = K / BK8;
-  for (int kt = 0; kt < nk; ++kt) {
-    stage_tile_glds8x4(gA, row_b, (long)kt * BK8, As, wave, lane);
-    stage_half_glds8(gB, row_b, (long)kt * BK8, 0, Bs, wave, lane);
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      v8i afrag[2], bfrag[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        int la = (wave_m + i * 32 + lane31) * 128 + ks * 64 + kq_b;
-        int lb = (wave_n + i * 32 + lane31) * 128 + ks * 64 + kq_b;
-        afrag[i] = load_frag32(As + swz8(la));
-        bfrag[i] = load_frag32(Bs + swz8(lb));
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          MFMA_FP8W_ASM(acc[i][j], afrag[i], bfrag[j]);
-    }
-    __syncthreads();
-  }
-  asm volatile("s_nop 15\ns_nop 15\ns_nop 2" :::);
-
-  const int c_col32 = lane & 31;
-  const int c_rowhi = (lane >> 5) * 4;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        int row = block_m + wave_m + i * 32 + (reg & 3) + 8 * (reg >> 2) + c_rowhi;
-        int col = block_n + wave_n + j * 32 + c_col32;
-        C[(long)row * N + col] = acc[i][j][reg];
-      }
-}
-
-// bf16 transplant of the fp8 winner above: 128x128 tile, BK=64
-// (128-B rows, so the same 16-KiB-tile stager and swz8 image apply
-// byte-for-byte), single-buffered 32 KiB LDS -> 4 blocks/CU, 32x32x16
-// ops with 2x2 tiles/wave (acc 64 VGPR). Tests whether the occupancy
-// lever that took fp8 from 1516 to 2052 TF also moves bf16.
-__global__ __launch_bounds__(256, 4) void mfma_gemm_bf16_128u(
-    const bf16* __restrict__ A, const bf16* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K) {
-  __shared__ char lds[2 * 16384];  // [A][B], single-buffered
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wave_m = (wave >> 1) * 64;
-  const int wave_n = (wave & 1) * 64;
-  const int block_m = blockIdx.y * BM;
-  const int block_n = blockIdx.x * BN;
-
-  const char* gA = (const char*)(A + (long)block_m * K);
-  const char* gB = (const char*)(Bt + (long)block_n * K);
-  const long row_b = (long)K * 2;
-
-  typedef __attribute__((ext_vector_type(16))) float f32x16v;
-  f32x16v acc[2][2] = {};
-  const int lane31 = lane & 31;
-  const int khalf_b = (lane >> 5) * 16;  // (l>>5)*8 bf16 = 16 B
-
-  char* As = &lds[0];
-  char* Bs = &lds[16384];
-  const int nk = K / 64;  // 64 bf16 = 128 B per K-tile
-  for (int kt = 0; kt < nk; ++kt) {
-    stage_tile_glds8x4(gA, row_b, (long)kt * 128, As, wave, lane);
-    stage_tile_glds8x4(gB, row_b, (long)kt * 128, Bs, wave, lane);
-    __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      bf16x8 af[2], bf[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        int la = (wave_m + i * 32 + lane31) * 128 + ks * 32 + khalf_b;
-        int lb = (wave_n + i * 32 + lane31) * 128 + ks * 32 + khalf_b;
-        af[i] = *(const bf16x8*)(As + swz8(la));
-        bf[i] = *(const bf16x8*)(Bs + swz8(lb));
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-              af[i], bf[j], acc[i][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-
-  const int c_col32 = lane & 31;
-  const int c_rowhi = (lane >> 5) * 4;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        int row = block_m + wave_m + i * 32 + (reg & 3) + 8 * (reg >> 2) + c_rowhi;
-        int col = block_n + wave_n + j * 32 + c_col32;
-        C[(long)row * N + col] = acc[i][j][reg];
-      }
-}
-
-// fp8 BK=128 at 3 blocks/CU via 1.5-buffering: B double-buffered
-// (prefetch overlaps compute), A single-buffered (restaged in a serial
-// window between two barriers) -> 48 KiB LDS/block. Tests the middle
-// point of the occupancy curve (2 blocks: 1505 TF, 4 blocks: 1586).
-__global__ __launch_bounds__(256, 3) void mfma_gemm_fp8_128t(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K) {
-  __shared__ char lds[3 * 16384];  // [A][B0][B1]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wave_m = (wave >> 1) * 64;
-  const int wave_n = (wave & 1) * 64;
-  const int block_m = blockIdx.y * BM;
-  const int block_n = blockIdx.x * BN;
-
-  const char* gA = A + (long)block_m * K;
-  const char* gB = Bt + (long)block_n * K;
-  const long row_b = (long)K;
-
-  f32x4 acc[4][4] = {};
-  const int lane15 = lane & 15;
-  const int kq_b = (lane >> 4) * 32;
-
-  const int nk = K / BK8;
-  char* As = &lds[0];
-  stage_tile_glds8x4(gA, row_b, 0, As, wave, lane);
-  stage_tile_glds8x4(gB, row_b, 0, &lds[16384], wave, lane);
-  __syncthreads();
-
-  for (int kt = 0; kt < nk; ++kt) {
-    char* Bs = &lds[16384 * (1 + (kt & 1))];
-    if (kt + 1 < nk)  // B prefetch overlaps this tile's compute
-      stage_tile_glds8x4(gB, row_b, (long)(kt + 1) * BK8,
-                         &lds[16384 * (1 + ((kt + 1) & 1))], wave, lane);
-    {
-      v8i afrag[4], bfrag[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int la = (wave_m + i * 16 + lane15) * 128 + kq_b;
-        int lb = (wave_n + i * 16 + lane15) * 128 + kq_b;
-        afrag[i] = load_frag32(As + swz8(la));
-        bfrag[i] = load_frag32(Bs + swz8(lb));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0, SCALE_ONE, 0, SCALE_ONE);
-    }
-    __syncthreads();  // all reads of As done (drains B prefetch too)
-    if (kt + 1 < nk) {
-      // serial A window: restage in place, land before next compute
-      stage_tile_glds8x4(gA, row_b, (long)(kt + 1) * BK8, As, wave, lane);
-      __syncthreads();
-    }
-  }
-
-  const int c_col = lane & 15;
-  const int c_row0 = (lane >> 4) * 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = block_m + wave_m + i * 16 + c_row0 + r;
-        int col = block_n + wave_n + j * 16 + c_col;
-        C[(long)row * N + col] = acc[i][j][r];
-      }
-}
-
-// fp8 step-3 variant with BK=256: doubles FLOPs per staged byte (the
-// PMC profiles show BOTH fp8 structures park ~53% on data waits with
-// identical MFMA busy — DMA/fetch-rate-bound, so feed each 32 KiB
-// stage twice the math). 128 KiB LDS -> 1 block/CU. Swizzle constraint
-// learned the hard way: XOR source bits must address whole fragments
-// (>= 32 B, byte bits >= 5) — a bit-4 XOR keyed on a ROW bit permutes
-// bytes inside the fragment differently for A-row m and B-row n,
-// breaking the MFMA's byte pairing (wrong results, caught by the
-// bitwise check). Bits 5-7 relocate fragments wholesale and are safe;
-// the residual is a 2-way bank conflict on rows r / r+8.
-constexpr int BK8L = 256;  // fp8 elements per K-tile (256 B rows)
-
-__device__ __forceinline__ int swz256(int off) {
-  return off ^ (((off >> 8) & 3) << 5) ^ (((off >> 10) & 1) << 7);
-}
-
-__device__ __forceinline__ void stage_tile_glds8w(
-    const char* gbase, long row_stride_b, long k0_b, char* lds_tile,
-    int wave, int lane) {
-#pragma unroll
-  for (int p = 0; p < 8; ++p) {
-    int base = (wave * 8 + p) * 1024;
-    int logical = swz256(base + lane * 16);
-    int row = logical >> 8;  // 256 B per row
-    int colb = logical & 255;
-    const char* g = gbase + (long)row * row_stride_b + k0_b + colb;
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)g,
-        (__attribute__((address_space(3))) void*)(lds_tile + base), 16, 0, 0);
-  }
-}
-
-__global__ __launch_bounds__(256, 1) void mfma_gemm_fp8_128w(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K) {
-  __shared__ char lds[2 * 2 * 32768];  // [buf][A|B][32 KiB]
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wave_m = (wave >> 1) * 64;
-  const int wave_n = (wave & 1) * 64;
-  const int block_m = blockIdx.y * BM;
-  const int block_n = blockIdx.x * BN;
-
-  const char* gA = A + (long)block_m * K;
-  const char* gB = Bt + (long)block_n * K;
-  const long row_b = (long)K;
-
-  f32x4 acc[4][4] = {};
-  const int lane15 = lane & 15;
-  const int kq_b = (lane >> 4) * 32;
-
-  const int nk = K / BK8L;
-  stage_tile_glds8w(gA, row_b, 0, &lds[0], wave, lane);
-  stage_tile_glds8w(gB, row_b, 0, &lds[32768], wave, lane);
-  __syncthreads();
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    char* As = &lds[buf * 2 * 32768];
-    char* Bs = As + 32768;
-    if (kt + 1 < nk) {
-      char* An = &lds[(buf ^ 1) * 2 * 32768];
-      stage_tile_glds8w(gA, row_b, (long)(kt + 1) * BK8L, An, wave, lane);
-      stage_tile_glds8w(gB, row_b, (long)(kt + 1) * BK8L, An + 32768, wave, lane);
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      v8i afrag[4], bfrag[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int la = (wave_m + i * 16 + lane15) * 256 + ks * 128 + kq_b;
-        int lb = (wave_n + i * 16 + lane15) * 256 + ks * 128 + kq_b;
-        afrag[i] = load_frag32(As + swz256(la));
-        bfrag[i] = load_frag32(Bs + swz256(lb));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0, SCALE_ONE, 0, SCALE_ONE);
-    }
-    __syncthreads();
-  }
-
-  const int c_col = lane & 15;
-  const int c_row0 = (lane >> 4) * 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = block_m + wave_m + i * 16 + c_row0 + r;
-        int col = block_n + wave_n + j * 16 + c_col;
-        C[(long)row * N + col] = acc[i][j][r];
-      }
-}
-
-// Deep-pipelined fp8: the same 8-phase 256x256 schedule as the bf16
-// template (identical 16 KiB half-tiles, prefetch map and vmcnt(6)
-// drains — the fp8 image has the same 128-B rows: 128 fp8 elements per
-// K-tile), with the scaled MFMA issued via INLINE ASM. The
-// __builtin_amdgcn_mfma_scale_* intrinsic's register-class constraints
-// interact pathologically with global_load_lds on ROCm 7.2: the
-// identical structure compiles to 180 VGPR/no-spill with bf16 MFMA but
-// 256 VGPR + ~1 KB/lane scratch with the intrinsic (and scratch ops
-// share the vm counter, corrupting counted-vmcnt drains). The asm form
-// compiles clean (162 VGPR in the bisect kernel). Hazards: inputs are
-// ds_read results (compiler inserts lgkm waits for asm data deps);
-// MFMA->MFMA on one accumulator is pipe-ordered; the only uncovered
-// RAW is accumulator->epilogue VALU, guarded by the post-loop s_nops.
-#define MFMA_FP8_ASM(ACCX, AOP, BOP)                                          \
-  asm volatile(                                                               \
-      "v_mfma_scale_f32_16x16x128_f8f6f4 %0, %1, %2, %0, %3, %4 "             \
-      "op_sel_hi:[0,0,0]"                                                     \
-      : "+v"(ACCX)                                                            \
-      : "v"(AOP), "v"(BOP), "v"(sc_reg), "v"(sc_reg))
-
-#define PHASE8D(buf, mh, nh, LOAD_A, LOAD_B, ACC, PREFETCH_STMT, DRAIN)       \
-  do {                                                                        \
-    if (LOAD_A) {                                                             \
-      char* Ah = slot_ptr(lds, 0, (buf), (mh));                               \
-      _Pragma("unroll") for (int i = 0; i < 4; ++i) {                         \
-        int lg = (wave_mq + i * 16 + lane15) * 128 + kq_b;                    \
-        a8[i] = *(const v8i*)(Ah + swz8(lg));                                 \
-      }                                                                       \
-    }                                                                         \
-    if (LOAD_B) {                                                             \
-      char* Bh = slot_ptr(lds, 1, (buf), (nh));                               \
-      _Pragma("unroll") for (int j = 0; j < 2; ++j) {                         \
-        int lg = (wave_nq + j * 16 + lane15) * 128 + kq_b;                    \
-        b8[j] = *(const v8i*)(Bh + swz8(lg));                                 \
-      }                                                                       \
-    }                                                                         \
-    PREFETCH_STMT;                                                            \
-    DRAIN;                                                                    \
-    __builtin_amdgcn_s_barrier();                                             \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                        \
-    __builtin_amdgcn_s_setprio(1);                                            \
-    _Pragma("unroll") for (int i = 0; i < 4; ++i)                             \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j)                         \
-            MFMA_FP8_ASM(ACC[i][j], a8[i], b8[j]);                            \
-    __builtin_amdgcn_s_setprio(0);                                            \
-    __builtin_amdgcn_s_barrier();                                             \
-  } while (0)
-
-__global__ __launch_bounds__(512, 1) void mfma_gemm_fp8_256(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K, int xcd_swizzle) {
-  __shared__ char lds[8 * HALF_B];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wave_mq = (wave >> 2) * 64;
-  const int wave_nq = (wave & 3) * 32;
-  const int lane15 = lane & 15;
-  const int kq_b = (lane >> 4) * 32;
-  int wg = blockIdx.y * gridDim.x + blockIdx.x;
-  if (xcd_swizzle) {
-    int nwg = gridDim.x * gridDim.y;
-    int q = nwg >> 3, r = nwg & 7;
-    int xcd = wg & 7, o = wg >> 3;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + o;
-  }
-  const int block_m = (wg / gridDim.x) * BM2;
-  const int block_n = (wg % gridDim.x) * BN2;
-
-  const char* gA = A + (long)block_m * K;
-  const char* gB = Bt + (long)block_n * K;
-  const long row_b = (long)K;
-  const int nk = K / BK8;
-
-  f32x4 acc00[4][2] = {}, acc01[4][2] = {}, acc10[4][2] = {}, acc11[4][2] = {};
-  v8i a8[4], b8[2];
-  int sc_reg;
-  asm("v_mov_b32 %0, 0x7f7f7f7f" : "=v"(sc_reg));  // e8m0 1.0 x4
-
-#define STAGE(op, buf, half, tile)                                            \
-  stage_half_glds8((op) == 0 ? gA : gB, row_b, (long)(tile) * BK8,            \
-                   (half) * 128, slot_ptr(lds, (op), (buf), (half)), wave,    \
-                   lane)
-
-  STAGE(0, 0, 0, 0);
-  STAGE(1, 0, 0, 0);
-  STAGE(0, 0, 1, 0);
-  STAGE(1, 0, 1, 0);
-  STAGE(0, 1, 0, 1);
-  STAGE(1, 1, 1, 1);
-  STAGE(0, 1, 1, 1);
-  __syncthreads();
-
-#define VM_DRAIN                                                              \
-  do {                                                                        \
-    if (tp + 4 >= nk)                                                         \
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                        \
-    else                                                                      \
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                        \
-  } while (0)
-
-  for (int tp = 0; tp < nk; tp += 2) {
-    PHASE8D(0, 0, 0, 1, 1, acc00, if (tp + 1 < nk) STAGE(1, 1, 0, tp + 1), );
-    PHASE8D(0, 0, 1, 0, 1, acc01, if (tp + 2 < nk) STAGE(0, 0, 0, tp + 2), );
-    PHASE8D(0, 1, 1, 1, 0, acc11, if (tp + 2 < nk) STAGE(1, 0, 1, tp + 2), );
-    PHASE8D(0, 1, 0, 0, 1, acc10, if (tp + 2 < nk) STAGE(0, 0, 1, tp + 2), VM_DRAIN);
-    PHASE8D(1, 0, 0, 1, 1, acc00, if (tp + 2 < nk) STAGE(1, 0, 0, tp + 2), );
-    PHASE8D(1, 0, 1, 0, 1, acc01, if (tp + 3 < nk) STAGE(0, 1, 0, tp + 3), );
-    PHASE8D(1, 1, 1, 1, 0, acc11, if (tp + 3 < nk) STAGE(1, 1, 1, tp + 3), );
-    PHASE8D(1, 1, 0, 0, 1, acc10, if (tp + 3 < nk) STAGE(0, 1, 1, tp + 3), VM_DRAIN);
-  }
-#undef VM_DRAIN
-#undef STAGE
-
-  // accumulator -> VALU RAW guard (the compiler cannot see through the
-  // asm MFMAs; ~34 cycles of nops once per kernel)
-  asm volatile("s_nop 15\ns_nop 15\ns_nop 2" :::);
-
-  const int c_col = lane & 15;
-  const int c_row0 = (lane >> 4) * 4;
-#define EPI(ACC, mh, nh)                                                      \
-  _Pragma("unroll") for (int i = 0; i < 4; ++i)                               \
-      _Pragma("unroll") for (int j = 0; j < 2; ++j)                           \
-      _Pragma("unroll") for (int r = 0; r < 4; ++r) {                         \
-    int row = block_m + (mh)*128 + wave_mq + i * 16 + c_row0 + r;             \
-    int col = block_n + (nh)*128 + wave_nq + j * 16 + c_col;                  \
-    C[(long)row * N + col] = ACC[i][j][r];                                    \
-  }
-  EPI(acc00, 0, 0)
-  EPI(acc01, 0, 1)
-  EPI(acc10, 1, 0)
-  EPI(acc11, 1, 1)
-#undef EPI
-}
-
-// fp8 GEMM uses the PROVEN step-3 structure (the 128x128 tile of
-// mfma_gemm_bf16): 4 waves, each computing 64x64 as 4x4 16-tiles, one
-// 16x16x128 scaled MFMA per tile pair per K-chunk (BK=128 fp8 = one
-// instruction's worth), double-buffered glds staging, __syncthreads
-// between K-steps. The deep-pipelined 256-tile shape was tried and
-// REJECTED for fp8: 32-B/lane fragments push the allocator past 256
-// VGPRs, the spill's scratch traffic miscounts the hand-counted vmcnt
-// drains (scratch ops share the vm counter), and results corrupt. The
-// step-3 shape holds acc at 64 VGPRs, fragments at 64, and its
-// __syncthreads drain is immune to incidental VMEM ops. The CDNA4
-// guide's ladder measured MX-fp8 K=128 at 1628 TF/s in exactly this
-// structure.
-__global__ __launch_bounds__(256, 2) void mfma_gemm_fp8_128(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K) {
-  __shared__ char lds[2 * 2 * 16384];  // [buf][A|B][16 KiB], one object
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;            // 0..3
-  const int wave_m = (wave >> 1) * 64;
-  const int wave_n = (wave & 1) * 64;
-  const int block_m = blockIdx.y * BM;
-  const int block_n = blockIdx.x * BN;
-
-  const char* gA = A + (long)block_m * K;
-  const char* gB = Bt + (long)block_n * K;
-  const long row_b = (long)K;  // bytes per row (1 B per element)
-
-  f32x4 acc[4][4] = {};  // 4x4 MFMA tiles of 16x16 per wave (64 VGPR)
-
-  const int lane15 = lane & 15;
-  const int kq_b = (lane >> 4) * 32;  // fragment k byte offset (32 fp8)
-
-  const int nk = K / BK8;
-  stage_tile_glds8x4(gA, row_b, 0, &lds[0], wave, lane);
-  stage_tile_glds8x4(gB, row_b, 0, &lds[16384], wave, lane);
-  __syncthreads();
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    char* As = &lds[buf * 2 * 16384];
-    char* Bs = As + 16384;
-    if (kt + 1 < nk) {
-      char* An = &lds[(buf ^ 1) * 2 * 16384];
-      stage_tile_glds8x4(gA, row_b, (long)(kt + 1) * BK8, An, wave, lane);
-      stage_tile_glds8x4(gB, row_b, (long)(kt + 1) * BK8, An + 16384, wave, lane);
-    }
-    {
-      v8i afrag[4], bfrag[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int la = (wave_m + i * 16 + lane15) * 128 + kq_b;
-        int lb = (wave_n + i * 16 + lane15) * 128 + kq_b;
-        afrag[i] = load_frag32(As + swz8(la));
-        bfrag[i] = load_frag32(Bs + swz8(lb));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0, SCALE_ONE, 0, SCALE_ONE);
-    }
-    __syncthreads();
-  }
-
-  // epilogue: 16x16 C/D map col=lane&15, row=(lane>>4)*4+r
-  const int c_col = lane & 15;
-  const int c_row0 = (lane >> 4) * 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        int row = block_m + wave_m + i * 16 + c_row0 + r;
-        int col = block_n + wave_n + j * 16 + c_col;
-        C[(long)row * N + col] = acc[i][j][r];
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------
-// VALU fp32 reference GEMM (independent ground truth; deliberately does
-// NOT share tiling or fragment code with the MFMA path).
-// One thread per C element, fp32 FMA chain over K.
-// ---------------------------------------------------------------------------
-__global__ void ref_gemm_f32(const bf16* __restrict__ A,
-                             const bf16* __restrict__ Bt,
-                             float* __restrict__ C, int M, int N, int K) {
-  int col = blockIdx.x * blockDim.x + threadIdx.x;
-  int row = blockIdx.y * blockDim.y + threadIdx.y;
-  if (row >= M || col >= N) return;
-  float acc = 0.f;
-  const bf16* a = A + (long)row * K;
-  const bf16* b = Bt + (long)col * K;
-  for (int k = 0; k < K; ++k) acc = fmaf((float)a[k], (float)b[k], acc);
-  C[(long)row * N + col] = acc;
-}
-
-// max |x-y| reduction over n elements -> out[0] (pre-zeroed)
-__global__ void max_abs_diff(const float* __restrict__ x,
-                             const float* __restrict__ y, long n,
-                             float* out) {
-  __shared__ float smax[256];
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  long stride = (long)gridDim.x * blockDim.x;
-  float m = 0.f;
-  for (; i < n; i += stride) {
-    float d = fabsf(x[i] - y[i]);
-    m = fmaxf(m, d);
-  }
-  smax[threadIdx.x] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) smax[threadIdx.x] = fmaxf(smax[threadIdx.x], smax[threadIdx.x + s]);
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    // fp32 max via atomicMax on the bit pattern (values are >= 0)
-    atomicMax((unsigned int*)out, __float_as_uint(smax[0]));
-  }
-}
-
-// FNV-1a style checksum of a float buffer -> 64-bit xor-fold (order
-// independent via per-element mix, so concurrent blocks are fine).
-__global__ void checksum_f32(const float* __restrict__ x, long n,
-                             unsigned long long* out) {
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  long stride = (long)gridDim.x * blockDim.x;
-  unsigned long long h = 0;
-  for (; i < n; i += stride) {
-    unsigned long long v = (unsigned long long)__float_as_uint(x[i]) + 0x9e3779b97f4a7c15ull * (unsigned long long)(i + 1);
-    v ^= v >> 33; v *= 0xff51afd7ed558ccdull; v ^= v >> 33;
-    h ^= v;
-  }
-  // xor-reduce wave -> block (LDS) -> ONE atomic per block. The first
-  // version did one atomic per wave: 4096 serialized atomicXors on a
-  // single address cost ~40 us — more than the whole hash sweep
-  // (bench kernel trace, profiles/bench_kernel_stats.csv).
-  for (int off = 32; off > 0; off >>= 1)
-    h ^= __shfl_down(h, off, 64);
-  __shared__ unsigned long long partial[4];
-  if ((threadIdx.x & 63) == 0) partial[threadIdx.x >> 6] = h;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long b = partial[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) b ^= partial[w];
-    atomicXor(out, b);
-  }
-}
-
-// ---------------------------------------------------------------------------
-// LDS probe: rotating write/read patterns across a 64 KiB LDS slab per
-// workgroup; validates every cell and measures aggregate LDS traffic.
-// ---------------------------------------------------------------------------
-constexpr int LDS_PROBE_WORDS = 16384;  // 64 KiB of uint32 per workgroup
-
-__global__ void lds_probe(uint32_t* __restrict__ fail_count, int rounds) {
-  __shared__ uint32_t slab[LDS_PROBE_WORDS];
-  const int tid = threadIdx.x;
-  const int nthreads = blockDim.x;
-  uint32_t local_fail = 0;
-  for (int r = 0; r < rounds; ++r) {
-    uint32_t salt = 0x9e3779b9u * (r + 1) + blockIdx.x;
-    for (int i = tid; i < LDS_PROBE_WORDS; i += nthreads)
-      slab[i] = (uint32_t)i * 2654435769u + salt;
-    __syncthreads();
-    // read back with a different (conflict-heavy, bank-rotating) stride
-    for (int i = tid; i < LDS_PROBE_WORDS; i += nthreads) {
-      int j = (i * 33 + r) & (LDS_PROBE_WORDS - 1);
-      uint32_t want = (uint32_t)j * 2654435769u + salt;
-      if (slab[j] != want) ++local_fail;
-    }
-    __syncthreads();
-  }
-  if (local_fail) atomicAdd(fail_count, local_fail);
-}
-
-// ---------------------------------------------------------------------------
-// HBM probe: float4 streaming copy (the measured-best pattern, ~79% of
-// the 8 TB/s peak per MI355X_MICROARCH.md) + spot validation.
-// ---------------------------------------------------------------------------
-__global__ void hbm_copy_f4(const float4v* __restrict__ src,
-                            float4v* __restrict__ dst, long n4) {
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  long stride = (long)gridDim.x * blockDim.x;
-  for (; i < n4; i += stride) dst[i] = src[i];
+  return launch_variant(kFp8Variants[kFp8_128s], A, Bt, C, M, N, K, 0);
 }
 
 // ===========================================================================
-// C API
-// ===========================================================================
-// ---------------------------------------------------------------------------
 // Persistent per-device probe context. The CC manager is a long-lived
 // daemon that attests after every transition: allocations, events and
 // the liveness scratch word are cached so steady-state probes pay only
 // kernel time (first call measured ~225 ms of hipMalloc/teardown
 // overhead at dim=1024; with the cached context AND the cached fp32
 // reference below, the warm probe is ~0.4 ms).
-// ---------------------------------------------------------------------------
+// ===========================================================================
 constexpr int kMaxDevices = 64;
 
 struct ProbeCtx {
@@ -1809,20 +280,34 @@ struct ProbeCtx {
 static ProbeCtx g_ctx[kMaxDevices];
 static std::mutex g_ctx_mu;
 
+// The context's device buffers, in allocation order. bytes == 0: not
+// allocated by ctx_acquire (the peer-leg buffers are lazy).
+struct CtxBuffer {
+  void** ptr;
+  size_t bytes;
+};
+
+static std::array<CtxBuffer, 13> ctx_buffers(ProbeCtx& c, long elems) {
+  return {{
+      {(void**)&c.dA, elems * sizeof(bf16)},
+      {(void**)&c.dB, elems * sizeof(bf16)},
+      {(void**)&c.dA8, (size_t)elems},
+      {(void**)&c.dB8, (size_t)elems},
+      {(void**)&c.dC, elems * sizeof(float)},
+      {(void**)&c.dRef, elems * sizeof(float)},
+      {(void**)&c.dHbm, elems * sizeof(float)},
+      {(void**)&c.dErr, sizeof(float)},
+      {(void**)&c.dSum, sizeof(unsigned long long)},
+      {(void**)&c.dFail, sizeof(uint32_t)},
+      {(void**)&c.dLive, sizeof(int)},
+      {(void**)&c.dPeerDst, 0},
+      {(void**)&c.dPeerSum, 0},
+  }};
+}
+
 static void ctx_release(ProbeCtx& c) {
-  if (c.dA) (void)hipFree(c.dA);
-  if (c.dB) (void)hipFree(c.dB);
-  if (c.dA8) (void)hipFree(c.dA8);
-  if (c.dB8) (void)hipFree(c.dB8);
-  if (c.dC) (void)hipFree(c.dC);
-  if (c.dRef) (void)hipFree(c.dRef);
-  if (c.dHbm) (void)hipFree(c.dHbm);
-  if (c.dErr) (void)hipFree(c.dErr);
-  if (c.dSum) (void)hipFree(c.dSum);
-  if (c.dFail) (void)hipFree(c.dFail);
-  if (c.dLive) (void)hipFree(c.dLive);
-  if (c.dPeerDst) (void)hipFree(c.dPeerDst);
-  if (c.dPeerSum) (void)hipFree(c.dPeerSum);
+  for (const CtxBuffer& b : ctx_buffers(c, 0))
+    if (*b.ptr) (void)hipFree(*b.ptr);
   if (c.ev0) (void)hipEventDestroy(c.ev0);
   if (c.ev1) (void)hipEventDestroy(c.ev1);
   c = ProbeCtx{};
@@ -1835,29 +320,15 @@ static hipError_t ctx_acquire(int device, int dim, ProbeCtx** out) {
     return hipSuccess;
   }
   ctx_release(c);
-  long elems = (long)dim * dim;
   hipError_t e;
-  if ((e = hipMalloc(&c.dA, elems * sizeof(bf16))) != hipSuccess) return e;
-  if ((e = hipMalloc(&c.dB, elems * sizeof(bf16))) != hipSuccess) return e;
-  if ((e = hipMalloc(&c.dA8, elems)) != hipSuccess) return e;
-  if ((e = hipMalloc(&c.dB8, elems)) != hipSuccess) return e;
-  if ((e = hipMalloc(&c.dC, elems * sizeof(float))) != hipSuccess) return e;
-  if ((e = hipMalloc(&c.dRef, elems * sizeof(float))) != hipSuccess) return e;
-  if ((e = hipMalloc(&c.dHbm, elems * sizeof(float))) != hipSuccess) return e;
-  if ((e = hipMalloc(&c.dErr, sizeof(float))) != hipSuccess) return e;
-  if ((e = hipMalloc(&c.dSum, sizeof(unsigned long long))) != hipSuccess) return e;
-  if ((e = hipMalloc(&c.dFail, sizeof(uint32_t))) != hipSuccess) return e;
-  if ((e = hipMalloc(&c.dLive, sizeof(int))) != hipSuccess) return e;
+  for (const CtxBuffer& b : ctx_buffers(c, (long)dim * dim))
+    if (b.bytes && (e = hipMalloc(b.ptr, b.bytes)) != hipSuccess) return e;
   if ((e = hipEventCreate(&c.ev0)) != hipSuccess) return e;
   if ((e = hipEventCreate(&c.ev1)) != hipSuccess) return e;
   c.dim = dim;
   *out = &c;
   return hipSuccess;
 }
-
-// The full self-contained attestation probe. gemm_dim: problem size
-// (square); 1024 for the post-reset gate (fast), 4096+ for perf
-// characterization. rep->ok = 1 iff every stage validated.
 
 extern "C" {
 
@@ -1900,12 +371,256 @@ struct CcAttestReport {
   int ok;
 };
 
-// Minimal liveness check: a real kernel launch must complete. Used as
-// the post-reset boot-wait gate (a device can answer property queries
-// from cached driver state while its command processor is wedged).
-__global__ void liveness_kernel(int* out) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) *out = 0x600D;
+}  // extern "C"
+
+// ===========================================================================
+// Probe legs. Each takes the context and the report and returns 0, a
+// HIP error (text in rep->error) or a negative probe status.
+// ===========================================================================
+
+// record, launch, record, sync: the launch's time on the null stream.
+// `launch` returns 0 or a status that aborts the leg.
+template <typename Launch>
+static int timed_ms(ProbeCtx* ctx, CcAttestReport* rep, double* ms,
+                    Launch launch) {
+  hipEvent_t ev0 = ctx->ev0, ev1 = ctx->ev1;
+  CC_CHECK(hipEventRecord(ev0, 0));
+  CC_TRY(launch());
+  CC_CHECK(hipEventRecord(ev1, 0));
+  CC_CHECK(hipEventSynchronize(ev1));
+  float f = 0.f;
+  (void)hipEventElapsedTime(&f, ev0, ev1);
+  *ms = (double)f;
+  return 0;
 }
+
+// copy one device word back, bit for bit
+template <typename T>
+static hipError_t read_back(const void* dptr, T* out) {
+  return hipMemcpy(out, dptr, sizeof(T), hipMemcpyDeviceToHost);
+}
+
+static int probe_bf16(ProbeCtx* ctx, CcAttestReport* rep) {
+  const int D = ctx->dim;
+  const long elems = (long)D * D;
+  bf16 *dA = ctx->dA, *dB = ctx->dB;
+  float *dC = ctx->dC, *dRef = ctx->dRef, *dErr = ctx->dErr;
+  unsigned long long* dSum = ctx->dSum;
+  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
+  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
+
+  // -- fill (asymmetric seeds: catches row/col-swapped layouts) --------
+  hipLaunchKernelGGL(fill_bf16_lcg, dim3(2048), dim3(256), 0, 0, dA, elems, 1u);
+  hipLaunchKernelGGL(fill_bf16_lcg, dim3(2048), dim3(256), 0, 0, dB, elems, 7u);
+
+  // -- MFMA GEMM (timed; warm once; best-fitting variant) --------------
+  launch_mfma_gemm(dA, dB, dC, D, D, D);
+  CC_CHECK(hipDeviceSynchronize());
+  CC_TRY(timed_ms(ctx, rep, &rep->gemm_ms, [&] {
+    launch_mfma_gemm(dA, dB, dC, D, D, D);
+    return 0;
+  }));
+  rep->gemm_tflops = 2.0 * D * (double)D * D / (rep->gemm_ms * 1e-3) / 1e12;
+
+  // -- VALU reference + compare ---------------------------------------
+  // The fill is deterministic per dim, so the fp32 reference is a
+  // constant: computed once per context (the dominant probe cost —
+  // ~1.9 ms of a 2.4 ms warm probe at dim 1024 — disappears from the
+  // steady-state transition path).
+  if (!ctx->ref_valid) {
+    CC_TRY(timed_ms(ctx, rep, &rep->ref_ms, [&] {
+      dim3 rblock(16, 16), rgrid((D + 15) / 16, (D + 15) / 16);
+      hipLaunchKernelGGL(ref_gemm_f32, rgrid, rblock, 0, 0, dA, dB, dRef, D, D,
+                         D);
+      return 0;
+    }));
+    ctx->ref_valid = 1;
+  } else {
+    rep->ref_ms = 0.0;  // cached
+  }
+
+  hipLaunchKernelGGL(max_abs_diff, dim3(1024), dim3(256), 0, 0, dC, dRef,
+                     elems, dErr);
+  hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0, dC, elems, dSum);
+  CC_CHECK(hipDeviceSynchronize());
+  CC_CHECK(read_back(dErr, &rep->max_abs_err));
+  CC_CHECK(read_back(dSum, &rep->checksum));
+  return 0;
+}
+
+// fp8 (MX-scaled) MFMA path: same integer values, same fp32 reference,
+// bitwise requirement; the PRODUCTION fp8 dispatch
+static int probe_fp8(ProbeCtx* ctx, CcAttestReport* rep) {
+  const int D = ctx->dim;
+  const long elems = (long)D * D;
+  float *dC = ctx->dC, *dErr = ctx->dErr;
+  hipLaunchKernelGGL(fill_fp8_lcg, dim3(2048), dim3(256), 0, 0, ctx->dA8,
+                     elems, 1u);
+  hipLaunchKernelGGL(fill_fp8_lcg, dim3(2048), dim3(256), 0, 0, ctx->dB8,
+                     elems, 7u);
+  if (launch_fp8_best(ctx->dA8, ctx->dB8, dC, D, D, D) != 0) return -6;
+  CC_CHECK(hipDeviceSynchronize());
+  CC_TRY(timed_ms(ctx, rep, &rep->fp8_ms, [&] {
+    return launch_fp8_best(ctx->dA8, ctx->dB8, dC, D, D, D) != 0 ? -6 : 0;
+  }));
+  rep->fp8_tflops = 2.0 * D * (double)D * D / (rep->fp8_ms * 1e-3) / 1e12;
+  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
+  hipLaunchKernelGGL(max_abs_diff, dim3(1024), dim3(256), 0, 0, dC, ctx->dRef,
+                     elems, dErr);
+  CC_CHECK(hipDeviceSynchronize());
+  CC_CHECK(read_back(dErr, &rep->fp8_max_abs_err));
+  return 0;
+}
+
+static int probe_lds(ProbeCtx* ctx, CcAttestReport* rep) {
+  uint32_t* dFail = ctx->dFail;
+  CC_CHECK(hipMemset(dFail, 0, sizeof(uint32_t)));
+  CC_TRY(timed_ms(ctx, rep, &rep->lds_ms, [&] {
+    hipLaunchKernelGGL(lds_probe, dim3(512), dim3(256), 0, 0, dFail, 8);
+    return 0;
+  }));
+  CC_CHECK(read_back(dFail, &rep->lds_failures));
+  return 0;
+}
+
+// HBM probe (dedicated dst: dRef is a cached constant)
+static int probe_hbm(ProbeCtx* ctx, CcAttestReport* rep) {
+  long n4 = (long)ctx->dim * ctx->dim / 4;
+  CC_TRY(timed_ms(ctx, rep, &rep->hbm_ms, [&] {
+    hipLaunchKernelGGL(hbm_copy_f4, dim3(4096), dim3(256), 0, 0,
+                       (const float4v*)ctx->dC, (float4v*)ctx->dHbm, n4);
+    return 0;
+  }));
+  rep->hbm_gbps = 2.0 * n4 * 16.0 / (rep->hbm_ms * 1e-3) / 1e9;
+  return 0;
+}
+
+// The xGMI leg hops to the peer device and back; any early return while
+// away must leave the calling thread on its own device again.
+struct DeviceHop {
+  int home;
+  bool away = false;
+  explicit DeviceHop(int device) : home(device) {}
+  hipError_t to(int peer) {
+    away = true;
+    return hipSetDevice(peer);
+  }
+  hipError_t back() {
+    hipError_t e = hipSetDevice(home);
+    away = e != hipSuccess;
+    return e;
+  }
+  ~DeviceHop() {
+    if (away) (void)hipSetDevice(home);
+  }
+};
+
+// xGMI peer visibility + traffic. Visibility alone attests nothing
+// about link integrity: for every accessible peer, move the live result
+// buffer across the link (SDMA over xGMI) and recompute its checksum ON
+// THE PEER. Per-link bandwidth is reported (xGMI is point-to-point,
+// 7 links x ~153 GB/s per GPU — each link is individually bound).
+static int probe_xgmi(ProbeCtx* ctx, CcAttestReport* rep) {
+  const int device = rep->device;
+  float* dC = ctx->dC;
+  unsigned long long* dSum = ctx->dSum;
+  int ndev = 0;
+  CC_CHECK(hipGetDeviceCount(&ndev));
+  rep->peer_count = ndev - 1;
+  if (ndev > kMaxDevices) ndev = kMaxDevices;
+  // Bounded per-link sample (2 MiB x 2 copies): on an 8-GPU hive the
+  // probe runs per device per transition and touches 7 links — an
+  // unbounded sample would dominate the transition step. 4 MiB per
+  // link is still real SDMA traffic with an on-peer checksum.
+  long bytes = (long)ctx->dim * ctx->dim * sizeof(float);
+  if (bytes > (2L << 20)) bytes = 2L << 20;
+  long sum_elems = bytes / sizeof(float);
+  // fresh source checksum over the sampled slice: dC now holds the
+  // fp8 result (the bf16-era rep->checksum no longer matches)
+  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
+  hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0, dC, sum_elems,
+                     dSum);
+  CC_CHECK(hipDeviceSynchronize());
+  unsigned long long src_sum = 0;
+  CC_CHECK(read_back(dSum, &src_sum));
+  // accessible peer list first; CC_ATTEST_XGMI_MAX_PEERS (0 = all)
+  // bounds how many links one probe samples — the scaling bench sets
+  // it so per-transition cost stays O(1) while the round-robin cursor
+  // still covers every link across consecutive probes
+  int acc[kMaxDevices];
+  int n_acc = 0;
+  for (int p = 0; p < ndev; ++p) {
+    if (p == device) continue;
+    int can = 0;
+    if (hipDeviceCanAccessPeer(&can, device, p) == hipSuccess && can)
+      acc[n_acc++] = p;
+  }
+  rep->peers_accessible = n_acc;
+  int max_peers = 0;
+  if (const char* mp = getenv("CC_ATTEST_XGMI_MAX_PEERS")) max_peers = atoi(mp);
+  int attempts = (max_peers > 0 && max_peers < n_acc) ? max_peers : n_acc;
+  rep->peers_attempted = attempts;
+  DeviceHop hop(device);
+  for (int t = 0; t < attempts; ++t) {
+    int p = acc[(ctx->peer_cursor + t) % (n_acc ? n_acc : 1)];
+    hipError_t pe = hipDeviceEnablePeerAccess(p, 0);
+    if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled) {
+      (void)hipGetLastError();  // clear; copy may still route via SDMA
+    }
+    // destination + checksum word live on the peer (cached there)
+    ProbeCtx& pc = g_ctx[p];
+    CC_CHECK(hop.to(p));
+    if (pc.peer_cap < bytes) {
+      if (pc.dPeerDst) (void)hipFree(pc.dPeerDst);
+      pc.dPeerDst = nullptr;
+      pc.peer_cap = 0;
+      if (hipMalloc(&pc.dPeerDst, bytes) != hipSuccess) {
+        CC_CHECK(hop.back());
+        continue;  // peer VRAM exhausted: counted accessible, not verified
+      }
+      pc.peer_cap = bytes;
+    }
+    if (!pc.dPeerSum &&
+        hipMalloc(&pc.dPeerSum, sizeof(unsigned long long)) != hipSuccess) {
+      CC_CHECK(hop.back());
+      continue;
+    }
+    CC_CHECK(hipMemset(pc.dPeerDst, 0, bytes));
+    CC_CHECK(hop.back());
+    // timed link traffic: kPeerIters copies of the result buffer
+    const int kPeerIters = 4;
+    double ms = 0.0;
+    CC_TRY(timed_ms(ctx, rep, &ms, [&] {
+      for (int it = 0; it < kPeerIters; ++it)
+        CC_CHECK(hipMemcpyPeerAsync(pc.dPeerDst, p, dC, device, bytes, 0));
+      return 0;
+    }));
+    rep->xgmi_ms += ms;
+    double gbps = (double)bytes * kPeerIters / (ms * 1e-3) / 1e9;
+    if (rep->xgmi_gbps_min == 0.0 || gbps < rep->xgmi_gbps_min)
+      rep->xgmi_gbps_min = gbps;
+    if (gbps > rep->xgmi_gbps_max) rep->xgmi_gbps_max = gbps;
+    // verify ON the peer: its own CUs must read back what crossed
+    CC_CHECK(hop.to(p));
+    CC_CHECK(hipMemset(pc.dPeerSum, 0, sizeof(unsigned long long)));
+    // checksum the SAMPLED slice only (sum_elems) — the peer buffer
+    // holds exactly `bytes`; summing all of dC would read out of bounds
+    hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0, pc.dPeerDst,
+                       sum_elems, pc.dPeerSum);
+    CC_CHECK(hipDeviceSynchronize());
+    unsigned long long peer_sum = 0;
+    CC_CHECK(read_back(pc.dPeerSum, &peer_sum));
+    CC_CHECK(hop.back());
+    if (peer_sum == src_sum) ++rep->peers_verified;
+  }
+  if (n_acc) ctx->peer_cursor = (ctx->peer_cursor + attempts) % n_acc;
+  return 0;
+}
+
+// ===========================================================================
+// C API
+// ===========================================================================
+extern "C" {
 
 int cc_device_alive(int device) {
   if (device < 0 || device >= kMaxDevices) return -1;
@@ -1943,50 +658,11 @@ int cc_device_index_for_bdf(int domain, int bus, int dev) {
   return -1;
 }
 
-// Launch the best-fitting MFMA GEMM variant (no sync).
-static int launch_mfma_gemm(const void* A, const void* Bt, void* C, int M,
-                            int N, int K) {
-  // SMALL/MID sizes: the 128-tile step-3 kernel wins decisively below
-  // ~2048² output — 407 vs 252 TF @2048³, 64 vs 51 @1024³
-  // (profiles/final_kernel_sweep_r02.json): the deep 256-tile pipeline
-  // cannot fill its phase schedule on a 64-block grid. Rule: take the
-  // 128-tile shape whenever ITS grid still fits <=1 block/CU.
-  if (M % BM == 0 && N % BN == 0 && K % BK == 0 &&
-      ((long)(N / BN) * (M / BM)) <= 256) {
-    dim3 grid(N / BN, M / BM);
-    hipLaunchKernelGGL(mfma_gemm_bf16, grid, dim3(256), 0, 0, (const bf16*)A,
-                       (const bf16*)Bt, (float*)C, M, N, K);
-    return 0;
-  }
-  if (M % BM2 == 0 && N % BN2 == 0 && K % (2 * BK2) == 0) {
-    dim3 grid(N / BN2, M / BM2);
-    // enable the XCD remap only past the 256 MiB Infinity Cache
-    long ws = 2L * K * (M + N) + 4L * M * N;
-    int swz_on = ws > (256L << 20) ? 1 : 0;
-    // measured across boxes: the 32x32x16 shape wins at <=1 block/CU
-    // grids (935 vs 848 TF @4096^3), the 16x16x32 shape past that
-    // (1129 vs 1096 @8192^3) — profiles/gemm_final_sweep_2026-09-13.json
-    if ((long)grid.x * grid.y <= 256)
-      hipLaunchKernelGGL(mfma_gemm_bf16_256w, grid, dim3(512), 0, 0,
-                         (const bf16*)A, (const bf16*)Bt, (float*)C, M, N, K,
-                         swz_on);
-    else
-      hipLaunchKernelGGL(mfma_gemm_bf16_256, grid, dim3(512), 0, 0,
-                         (const bf16*)A, (const bf16*)Bt, (float*)C, M, N, K,
-                         swz_on);
-    return 0;
-  }
-  if (M % BM || N % BN || K % BK) return -2;
-  dim3 grid(N / BN, M / BM);
-  hipLaunchKernelGGL(mfma_gemm_bf16, grid, dim3(256), 0, 0, (const bf16*)A,
-                     (const bf16*)Bt, (float*)C, M, N, K);
-  return 0;
-}
-
 // Run the bf16 MFMA GEMM on caller-provided device buffers (e.g. torch
-// tensors): C[M,N] = A[M,K] @ Bt[N,K]^T. M,N multiples of 128, K of 32
-// (the deep-pipelined 256x256 variant is selected automatically when
-// M,N are multiples of 256 and K of 128).
+// tensors): C[M,N] = A[M,K] @ Bt[N,K]^T. M,N multiples of 128, K of 64
+// (the deep-pipelined 256x256 variants are selected automatically when
+// M,N are multiples of 256, K of 128 and the 128-tile grid exceeds one
+// block per CU).
 int cc_mfma_gemm_bf16(int device, const void* A, const void* Bt, void* C,
                       int M, int N, int K) {
   if (hipSetDevice(device) != hipSuccess) return -3;
@@ -1995,165 +671,24 @@ int cc_mfma_gemm_bf16(int device, const void* A, const void* Bt, void* C,
   return (int)hipDeviceSynchronize();
 }
 
-// Force a specific bf16 variant (perf characterization / A-B):
-// 0 = 128x128 step-3, 1 = 256x256 8-phase (16x16 op),
-// 2 = 256x256 8-phase (32x32 op), 3 = 128x128 single-buffered
-// 4-blocks/CU (measured slower than the deep pipeline — kept as the
-// recorded negative arm of the occupancy series, BASELINE.md).
+// Force a specific bf16 variant (perf characterization / A-B); `which`
+// indexes kBf16Variants, anything else runs variant 0.
 int cc_mfma_gemm_bf16_variant(int device, const void* A, const void* Bt,
                               void* C, int M, int N, int K, int which) {
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  if (which == 3) {
-    if (M % BM || N % BN || K % 64) return -2;
-    dim3 grid(N / BN, M / BM);
-    hipLaunchKernelGGL(mfma_gemm_bf16_128u, grid, dim3(256), 0, 0,
-                       (const bf16*)A, (const bf16*)Bt, (float*)C, M, N, K);
-  } else if (which == 1 || which == 2) {
-    if (M % BM2 || N % BN2 || K % (2 * BK2)) return -2;
-    dim3 grid(N / BN2, M / BM2);
-    long ws = 2L * K * (M + N) + 4L * M * N;
-    int swz_on = ws > (256L << 20) ? 1 : 0;
-    if (which == 2)
-      hipLaunchKernelGGL(mfma_gemm_bf16_256w, grid, dim3(512), 0, 0,
-                         (const bf16*)A, (const bf16*)Bt, (float*)C, M, N, K,
-                         swz_on);
-    else
-      hipLaunchKernelGGL(mfma_gemm_bf16_256, grid, dim3(512), 0, 0,
-                         (const bf16*)A, (const bf16*)Bt, (float*)C, M, N, K,
-                         swz_on);
-  } else {
-    if (M % BM || N % BN || K % BK) return -2;
-    dim3 grid(N / BN, M / BM);
-    hipLaunchKernelGGL(mfma_gemm_bf16, grid, dim3(256), 0, 0, (const bf16*)A,
-                       (const bf16*)Bt, (float*)C, M, N, K);
-  }
-  return (int)hipDeviceSynchronize();
+  return run_forced_variant(kBf16Variants, 4, 2, device, A, Bt, C, M, N, K,
+                            which);
 }
 
-// Force a specific fp8 variant (perf characterization / A-B):
-// 0 = 128-tile BK=128 double-buffered (2 blocks/CU),
-// 1 = 256-tile deep pipeline, 2 = 128-tile BK=256 (1 block/CU),
-// 3 = BK=64 32x32-op (4 blocks/CU), 4 = BK=128 1.5-buffered
-// (3 blocks/CU), 5 = BK=128 SINGLE-buffered (4 blocks/CU — the
-// production dispatch winner), 6 = 256x128 tile, 512 threads
-// (2 blocks/CU), 7 = producer/consumer wave split (4 stage waves +
-// 4 MFMA waves, LDS-flag handoff, no block barrier in the K loop).
-// Measured ladder in BASELINE.md.
+// Force a specific fp8 variant (perf characterization / A-B); `which`
+// indexes kFp8Variants (0-14), anything else runs variant 0.
 int cc_mfma_gemm_fp8_variant(int device, const void* A, const void* Bt,
                              void* C, int M, int N, int K, int which) {
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  if (which == 14) {
-    // forced split-K (dispatch's tiny-grid shape at any size)
-    if (M % BM || N % BN || K % BK8) return -2;
-    dim3 grid(N / BN, M / BM);
-    int nk = K / BK8;
-    long blocks = (long)grid.x * grid.y;
-    int S = (int)(1024 / (blocks ? blocks : 1));
-    if (S > nk) S = nk;
-    if (S < 2) S = 2;
-    if (hipMemsetAsync(C, 0, (long)M * N * sizeof(float), 0) != hipSuccess)
-      return -4;
-    dim3 g(grid.x, grid.y, S);
-    hipLaunchKernelGGL(mfma_gemm_fp8_128sk, g, dim3(256), 0, 0,
-                       (const char*)A, (const char*)Bt, (float*)C, M, N, K);
-  } else if (which == 13) {
-    // 256x256 @ 1 block/CU, persistent fragments, full double buffer
-    if (M % 256 || N % 256 || K % BK8) return -2;
-    dim3 grid(N / 256, M / 256);
-    hipLaunchKernelGGL(mfma_gemm_fp8_256x, grid, dim3(512), 0, 0,
-                       (const char*)A, (const char*)Bt, (float*)C, M, N, K);
-  } else if (which == 7 || which == 9) {
-    if (M % BM || N % BN || K % BK8) return -2;
-    dim3 grid(N / BN, M / BM);
-    hipLaunchKernelGGL(mfma_gemm_fp8_128pc, grid, dim3(512), 0, 0,
-                       (const char*)A, (const char*)Bt, (float*)C, M, N, K,
-                       which == 9 ? 1 : 0);
-  } else if (which == 8 || which == 10 || which == 11 || which == 12) {
-    // 8 = XCD remap, 10 = timing skew, 11 = kt rotation, 12 = skew+rot
-    if (M % BM || N % BN || K % BK8) return -2;
-    dim3 grid(N / BN, M / BM);
-    int opts = which == 8 ? 1 : which == 10 ? 2 : which == 11 ? 4 : 6;
-    hipLaunchKernelGGL(mfma_gemm_fp8_128u, grid, dim3(256), 0, 0,
-                       (const char*)A, (const char*)Bt, (float*)C, M, N, K,
-                       opts);
-  } else if (which == 6) {
-    if (M % 256 || N % BN || K % BK8) return -2;
-    dim3 grid(N / BN, M / 256);
-    hipLaunchKernelGGL(mfma_gemm_fp8_256u, grid, dim3(512), 0, 0,
-                       (const char*)A, (const char*)Bt, (float*)C, M, N, K);
-  } else if (which == 5) {
-    if (M % BM || N % BN || K % BK8) return -2;
-    dim3 grid(N / BN, M / BM);
-    hipLaunchKernelGGL(mfma_gemm_fp8_128u, grid, dim3(256), 0, 0,
-                       (const char*)A, (const char*)Bt, (float*)C, M, N, K, 0);
-  } else if (which == 4) {
-    if (M % BM || N % BN || K % BK8) return -2;
-    dim3 grid(N / BN, M / BM);
-    hipLaunchKernelGGL(mfma_gemm_fp8_128t, grid, dim3(256), 0, 0,
-                       (const char*)A, (const char*)Bt, (float*)C, M, N, K);
-  } else if (which == 3) {
-    if (M % BM || N % BN || K % 64) return -2;
-    dim3 grid(N / BN, M / BM);
-    hipLaunchKernelGGL(mfma_gemm_fp8_128s, grid, dim3(256), 0, 0,
-                       (const char*)A, (const char*)Bt, (float*)C, M, N, K);
-  } else if (which == 2) {
-    if (M % BM || N % BN || K % BK8L) return -2;
-    dim3 grid(N / BN, M / BM);
-    hipLaunchKernelGGL(mfma_gemm_fp8_128w, grid, dim3(256), 0, 0,
-                       (const char*)A, (const char*)Bt, (float*)C, M, N, K);
-  } else if (which == 1) {
-    if (M % BM2 || N % BN2 || K % (2 * BK8)) return -2;
-    dim3 grid(N / BN2, M / BM2);
-    long ws = (long)K * (M + N) + 4L * M * N;
-    hipLaunchKernelGGL(mfma_gemm_fp8_256, grid, dim3(512), 0, 0,
-                       (const char*)A, (const char*)Bt, (float*)C, M, N, K,
-                       ws > (256L << 20) ? 1 : 0);
-  } else {
-    if (M % BM || N % BN || K % BK8) return -2;
-    dim3 grid(N / BN, M / BM);
-    hipLaunchKernelGGL(mfma_gemm_fp8_128, grid, dim3(256), 0, 0,
-                       (const char*)A, (const char*)Bt, (float*)C, M, N, K);
-  }
-  return (int)hipDeviceSynchronize();
-}
-
-// Best-fitting fp8 launch (no sync). Measured dispatch policy:
-// - <=256 blocks (<=1 block/CU): producer/consumer wave split (stage
-//   windows fully exposed there; +16% measured, fp8_ab_1/boundary);
-// - past 1 block/CU: the single-buffered 4-blocks/CU barrier shape
-//   (occupancy wins; 2125 vs 1811 @8k).
-// Split-K for tiny grids was built and MEASURED OUT (fp8_sk.json:
-// 50.7 vs 111.5 TF @1024 — sub-2048 sizes are launch-latency bound,
-// not occupancy bound; the C memset + atomic RMW are pure overhead).
-// K%64-only shapes fall back to the BK=64 4-blocks/CU kernel.
-static int launch_fp8_best(const void* A, const void* Bt, void* C, int M,
-                           int N, int K) {
-  if (M % BM || N % BN) return -2;
-  dim3 grid(N / BN, M / BM);
-  long ws = (long)K * (M + N) + 4L * M * N;
-  int swz_on = ws > (256L << 20) ? 1 : 0;
-  if (K % BK8 == 0) {
-    long blocks = (long)grid.x * grid.y;
-    if (blocks <= 256)
-      hipLaunchKernelGGL(mfma_gemm_fp8_128pc, grid, dim3(512), 0, 0,
-                         (const char*)A, (const char*)Bt, (float*)C, M, N, K,
-                         swz_on);
-    else
-      hipLaunchKernelGGL(mfma_gemm_fp8_128u, grid, dim3(256), 0, 0,
-                         (const char*)A, (const char*)Bt, (float*)C, M, N, K,
-                         swz_on);
-    return 0;
-  }
-  if (K % 64 == 0) {
-    hipLaunchKernelGGL(mfma_gemm_fp8_128s, grid, dim3(256), 0, 0,
-                       (const char*)A, (const char*)Bt, (float*)C, M, N, K);
-    return 0;
-  }
-  return -2;
+  return run_forced_variant(kFp8Variants, 15, 1, device, A, Bt, C, M, N, K,
+                            which);
 }
 
 // MX-scaled fp8 (e4m3) GEMM: C[M,N] = A[M,K] @ Bt[N,K]^T, fp8 inputs,
-// fp32 out. M,N multiples of 128; K multiple of 128.
+// fp32 out. M,N multiples of 128; K multiple of 64.
 int cc_mfma_gemm_fp8(int device, const void* A, const void* Bt, void* C,
                      int M, int N, int K) {
   if (hipSetDevice(device) != hipSuccess) return -3;
@@ -2173,12 +708,9 @@ int cc_ref_gemm_f32(int device, const void* A, const void* Bt, void* C,
   return (int)hipDeviceSynchronize();
 }
 
-static double event_ms(hipEvent_t a, hipEvent_t b) {
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, a, b);
-  return (double)ms;
-}
-
+// The full self-contained attestation probe. gemm_dim: problem size
+// (square); 1024 for the post-reset gate (fast), 4096+ for perf
+// characterization. rep->ok = 1 iff every stage validated.
 int cc_attest_device(int device, int gemm_dim, struct CcAttestReport* rep) {
   if (!rep) return -1;
   __builtin_memset(rep, 0, sizeof(*rep));
@@ -2193,210 +725,17 @@ int cc_attest_device(int device, int gemm_dim, struct CcAttestReport* rep) {
 
   const int D = (gemm_dim / BM) * BM > 0 ? (gemm_dim / BM) * BM : BM;
   rep->gemm_m = rep->gemm_n = rep->gemm_k = D;
-  long elems = (long)D * D;
 
   std::lock_guard<std::mutex> lk(g_ctx_mu);
   if (device < 0 || device >= kMaxDevices) return -5;
   ProbeCtx* ctx = nullptr;
   CC_CHECK(ctx_acquire(device, D, &ctx));
-  bf16 *dA = ctx->dA, *dB = ctx->dB;
-  float *dC = ctx->dC, *dRef = ctx->dRef, *dErr = ctx->dErr;
-  unsigned long long* dSum = ctx->dSum;
-  hipEvent_t ev0 = ctx->ev0, ev1 = ctx->ev1;
-  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
-  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
 
-  // -- fill (asymmetric seeds: catches row/col-swapped layouts) --------
-  hipLaunchKernelGGL(fill_bf16_lcg, dim3(2048), dim3(256), 0, 0, dA, elems, 1u);
-  hipLaunchKernelGGL(fill_bf16_lcg, dim3(2048), dim3(256), 0, 0, dB, elems, 7u);
-
-  // -- MFMA GEMM (timed; warm once; best-fitting variant) --------------
-  launch_mfma_gemm(dA, dB, dC, D, D, D);
-  CC_CHECK(hipDeviceSynchronize());
-  CC_CHECK(hipEventRecord(ev0, 0));
-  launch_mfma_gemm(dA, dB, dC, D, D, D);
-  CC_CHECK(hipEventRecord(ev1, 0));
-  CC_CHECK(hipEventSynchronize(ev1));
-  rep->gemm_ms = event_ms(ev0, ev1);
-  rep->gemm_tflops = 2.0 * D * (double)D * D / (rep->gemm_ms * 1e-3) / 1e12;
-
-  // -- VALU reference + compare ---------------------------------------
-  // The fill is deterministic per dim, so the fp32 reference is a
-  // constant: computed once per context (the dominant probe cost —
-  // ~1.9 ms of a 2.4 ms warm probe at dim 1024 — disappears from the
-  // steady-state transition path).
-  if (!ctx->ref_valid) {
-    CC_CHECK(hipEventRecord(ev0, 0));
-    {
-      dim3 rblock(16, 16), rgrid((D + 15) / 16, (D + 15) / 16);
-      hipLaunchKernelGGL(ref_gemm_f32, rgrid, rblock, 0, 0, dA, dB, dRef, D, D,
-                         D);
-    }
-    CC_CHECK(hipEventRecord(ev1, 0));
-    CC_CHECK(hipEventSynchronize(ev1));
-    rep->ref_ms = event_ms(ev0, ev1);
-    ctx->ref_valid = 1;
-  } else {
-    rep->ref_ms = 0.0;  // cached
-  }
-
-  hipLaunchKernelGGL(max_abs_diff, dim3(1024), dim3(256), 0, 0, dC, dRef,
-                     elems, dErr);
-  hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0, dC, elems, dSum);
-  CC_CHECK(hipDeviceSynchronize());
-  unsigned int err_bits = 0;
-  CC_CHECK(hipMemcpy(&err_bits, dErr, sizeof(err_bits), hipMemcpyDeviceToHost));
-  float max_err;
-  __builtin_memcpy(&max_err, &err_bits, sizeof(max_err));
-  rep->max_abs_err = max_err;
-  CC_CHECK(hipMemcpy(&rep->checksum, dSum, sizeof(rep->checksum),
-                     hipMemcpyDeviceToHost));
-
-  // -- fp8 (MX-scaled) MFMA path: same integer values, same fp32
-  // reference, bitwise requirement -------------------------------------
-  hipLaunchKernelGGL(fill_fp8_lcg, dim3(2048), dim3(256), 0, 0, ctx->dA8,
-                     elems, 1u);
-  hipLaunchKernelGGL(fill_fp8_lcg, dim3(2048), dim3(256), 0, 0, ctx->dB8,
-                     elems, 7u);
-  {
-    // the PRODUCTION fp8 dispatch (split-K fills the chip at the
-    // probe's 64-block grid; p/c or barrier shape at larger dims)
-    if (launch_fp8_best(ctx->dA8, ctx->dB8, dC, D, D, D) != 0) return -6;
-    CC_CHECK(hipDeviceSynchronize());
-    CC_CHECK(hipEventRecord(ev0, 0));
-    if (launch_fp8_best(ctx->dA8, ctx->dB8, dC, D, D, D) != 0) return -6;
-    CC_CHECK(hipEventRecord(ev1, 0));
-    CC_CHECK(hipEventSynchronize(ev1));
-    rep->fp8_ms = event_ms(ev0, ev1);
-    rep->fp8_tflops = 2.0 * D * (double)D * D / (rep->fp8_ms * 1e-3) / 1e12;
-    CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
-    hipLaunchKernelGGL(max_abs_diff, dim3(1024), dim3(256), 0, 0, dC, dRef,
-                       elems, dErr);
-    CC_CHECK(hipDeviceSynchronize());
-    unsigned int e8 = 0;
-    CC_CHECK(hipMemcpy(&e8, dErr, sizeof(e8), hipMemcpyDeviceToHost));
-    float f8err;
-    __builtin_memcpy(&f8err, &e8, sizeof(f8err));
-    rep->fp8_max_abs_err = f8err;
-  }
-
-  // -- LDS probe -------------------------------------------------------
-  uint32_t* dFail = ctx->dFail;
-  CC_CHECK(hipMemset(dFail, 0, sizeof(uint32_t)));
-  CC_CHECK(hipEventRecord(ev0, 0));
-  hipLaunchKernelGGL(lds_probe, dim3(512), dim3(256), 0, 0, dFail, 8);
-  CC_CHECK(hipEventRecord(ev1, 0));
-  CC_CHECK(hipEventSynchronize(ev1));
-  rep->lds_ms = event_ms(ev0, ev1);
-  CC_CHECK(hipMemcpy(&rep->lds_failures, dFail, sizeof(uint32_t),
-                     hipMemcpyDeviceToHost));
-
-  // -- HBM probe (dedicated dst: dRef is a cached constant now) --------
-  long n4 = elems / 4;
-  CC_CHECK(hipEventRecord(ev0, 0));
-  hipLaunchKernelGGL(hbm_copy_f4, dim3(4096), dim3(256), 0, 0,
-                     (const float4v*)dC, (float4v*)ctx->dHbm, n4);
-  CC_CHECK(hipEventRecord(ev1, 0));
-  CC_CHECK(hipEventSynchronize(ev1));
-  rep->hbm_ms = event_ms(ev0, ev1);
-  rep->hbm_gbps = 2.0 * n4 * 16.0 / (rep->hbm_ms * 1e-3) / 1e9;
-
-  // -- xGMI peer visibility + traffic ---------------------------------
-  // Visibility alone attests nothing about link integrity: for every
-  // accessible peer, move the live result buffer across the link (SDMA
-  // over xGMI) and recompute its checksum ON THE PEER. Per-link
-  // bandwidth is reported (xGMI is point-to-point, 7 links x ~153 GB/s
-  // per GPU — each link is individually bound).
-  int ndev = 0;
-  CC_CHECK(hipGetDeviceCount(&ndev));
-  rep->peer_count = ndev - 1;
-  if (ndev > kMaxDevices) ndev = kMaxDevices;
-  // Bounded per-link sample (2 MiB x 2 copies): on an 8-GPU hive the
-  // probe runs per device per transition and touches 7 links — an
-  // unbounded sample would dominate the transition step. 4 MiB per
-  // link is still real SDMA traffic with an on-peer checksum.
-  long bytes = elems * sizeof(float);
-  if (bytes > (2L << 20)) bytes = 2L << 20;
-  long sum_elems = bytes / sizeof(float);
-  // fresh source checksum over the sampled slice: dC now holds the
-  // fp8 result (the bf16-era rep->checksum no longer matches)
-  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
-  hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0, dC, sum_elems,
-                     dSum);
-  CC_CHECK(hipDeviceSynchronize());
-  unsigned long long src_sum = 0;
-  CC_CHECK(hipMemcpy(&src_sum, dSum, sizeof(src_sum), hipMemcpyDeviceToHost));
-  // accessible peer list first; CC_ATTEST_XGMI_MAX_PEERS (0 = all)
-  // bounds how many links one probe samples — the scaling bench sets
-  // it so per-transition cost stays O(1) while the round-robin cursor
-  // still covers every link across consecutive probes
-  int acc[kMaxDevices];
-  int n_acc = 0;
-  for (int p = 0; p < ndev; ++p) {
-    if (p == device) continue;
-    int can = 0;
-    if (hipDeviceCanAccessPeer(&can, device, p) == hipSuccess && can)
-      acc[n_acc++] = p;
-  }
-  rep->peers_accessible = n_acc;
-  int max_peers = 0;
-  if (const char* mp = getenv("CC_ATTEST_XGMI_MAX_PEERS")) max_peers = atoi(mp);
-  int attempts = (max_peers > 0 && max_peers < n_acc) ? max_peers : n_acc;
-  rep->peers_attempted = attempts;
-  for (int t = 0; t < attempts; ++t) {
-    int p = acc[(ctx->peer_cursor + t) % (n_acc ? n_acc : 1)];
-    hipError_t pe = hipDeviceEnablePeerAccess(p, 0);
-    if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled) {
-      (void)hipGetLastError();  // clear; copy may still route via SDMA
-    }
-    // destination + checksum word live on the peer (cached there)
-    ProbeCtx& pc = g_ctx[p];
-    CC_CHECK(hipSetDevice(p));
-    if (pc.peer_cap < bytes) {
-      if (pc.dPeerDst) (void)hipFree(pc.dPeerDst);
-      pc.dPeerDst = nullptr;
-      pc.peer_cap = 0;
-      if (hipMalloc(&pc.dPeerDst, bytes) != hipSuccess) {
-        CC_CHECK(hipSetDevice(device));
-        continue;  // peer VRAM exhausted: counted accessible, not verified
-      }
-      pc.peer_cap = bytes;
-    }
-    if (!pc.dPeerSum &&
-        hipMalloc(&pc.dPeerSum, sizeof(unsigned long long)) != hipSuccess) {
-      CC_CHECK(hipSetDevice(device));
-      continue;
-    }
-    CC_CHECK(hipMemset(pc.dPeerDst, 0, bytes));
-    CC_CHECK(hipSetDevice(device));
-    // timed link traffic: kPeerIters copies of the result buffer
-    const int kPeerIters = 4;
-    CC_CHECK(hipEventRecord(ev0, 0));
-    for (int it = 0; it < kPeerIters; ++it)
-      CC_CHECK(hipMemcpyPeerAsync(pc.dPeerDst, p, dC, device, bytes, 0));
-    CC_CHECK(hipEventRecord(ev1, 0));
-    CC_CHECK(hipEventSynchronize(ev1));
-    double ms = event_ms(ev0, ev1);
-    rep->xgmi_ms += ms;
-    double gbps = (double)bytes * kPeerIters / (ms * 1e-3) / 1e9;
-    if (rep->xgmi_gbps_min == 0.0 || gbps < rep->xgmi_gbps_min)
-      rep->xgmi_gbps_min = gbps;
-    if (gbps > rep->xgmi_gbps_max) rep->xgmi_gbps_max = gbps;
-    // verify ON the peer: its own CUs must read back what crossed
-    CC_CHECK(hipSetDevice(p));
-    CC_CHECK(hipMemset(pc.dPeerSum, 0, sizeof(unsigned long long)));
-    // checksum the SAMPLED slice only (sum_elems) — the peer buffer
-    // holds exactly `bytes`; summing `elems` would read out of bounds
-    hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0, pc.dPeerDst,
-                       sum_elems, pc.dPeerSum);
-    CC_CHECK(hipDeviceSynchronize());
-    unsigned long long peer_sum = 0;
-    CC_CHECK(hipMemcpy(&peer_sum, pc.dPeerSum, sizeof(peer_sum),
-                       hipMemcpyDeviceToHost));
-    CC_CHECK(hipSetDevice(device));
-    if (peer_sum == src_sum) ++rep->peers_verified;
-  }
-  if (n_acc) ctx->peer_cursor = (ctx->peer_cursor + attempts) % n_acc;
+  CC_TRY(probe_bf16(ctx, rep));
+  CC_TRY(probe_fp8(ctx, rep));
+  CC_TRY(probe_lds(ctx, rep));
+  CC_TRY(probe_hbm(ctx, rep));
+  CC_TRY(probe_xgmi(ctx, rep));
 
   rep->ok = (rep->max_abs_err == 0.0f) && (rep->fp8_max_abs_err == 0.0f) &&
                     (rep->lds_failures == 0) && (rep->gemm_tflops > 0.0) &&

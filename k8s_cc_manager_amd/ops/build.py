@@ -21,13 +21,14 @@ HIPCC = os.environ.get("HIPCC", "hipcc")
 ARCH = os.environ.get("CC_GPU_ARCH", "gfx950")
 
 
+def sources_mtime() -> float:
+    """Newest mtime over every ``*.hip`` here: ``SRC`` includes the rest."""
+    return max(p.stat().st_mtime for p in OPS_DIR.glob("*.hip"))
+
+
 def build(force: bool = False) -> Path:
-    """Compile the attestation library if the source is newer."""
-    if (
-        not force
-        and LIB.exists()
-        and LIB.stat().st_mtime >= SRC.stat().st_mtime
-    ):
+    """Compile the attestation library if any source is newer."""
+    if not force and LIB.exists() and LIB.stat().st_mtime >= sources_mtime():
         return LIB
     cmd = [
         HIPCC,

@@ -37,12 +37,14 @@ def build_variants():
     """Build the experiment .so set if missing (they are gitignored)."""
     import subprocess
 
-    src = Path(__file__).resolve().parent.parent / "k8s_cc_manager_amd/ops/attest_kernels.hip"
+    ops = Path(__file__).resolve().parent.parent / "k8s_cc_manager_amd/ops"
+    src = ops / "attest_kernels.hip"  # includes the other *.hip files
+    newest = max(p.stat().st_mtime for p in ops.glob("*.hip"))
     outdir = Path("expbuild")
     outdir.mkdir(exist_ok=True)
     for name, flags in VARIANT_FLAGS.items():
         out = outdir / f"libcc_{name}.so"
-        if out.exists() and out.stat().st_mtime >= src.stat().st_mtime:
+        if out.exists() and out.stat().st_mtime >= newest:
             continue
         subprocess.run(
             ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared",

@@ -99,6 +99,25 @@ def test_mfma_gemm_bf16_4blk_bitwise(attest):
         assert torch.equal(c, ref), f"trial {trial} mismatch"
 
 
+@pytest.mark.parametrize("which", [0, 1, 2, 3])
+def test_mfma_gemm_bf16_variants_nonsquare_bitwise(attest, which):
+    """Every forced bf16 variant on a non-square shape (2x4 blocks for
+    the 128-tile kernels, 1x2 for the 256-tile ones): a swapped M/N in
+    the shared epilogue or block mapping is a bitwise mismatch."""
+    m, n, k = 256, 512, 512
+    torch.manual_seed(which)
+    a = (torch.randint(-2, 2, (m, k), device="cuda")).bfloat16()
+    bt = (torch.randint(-2, 2, (n, k), device="cuda")).bfloat16()
+    ref = a.float() @ bt.float().t()
+    for trial in range(5):
+        c = torch.empty(m, n, device="cuda", dtype=torch.float32)
+        attest.mfma_gemm_bf16_variant(
+            0, a.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k, which
+        )
+        torch.cuda.synchronize()
+        assert torch.equal(c, ref), f"which={which} trial={trial}"
+
+
 def test_mfma_gemm_256_integer_exact_race_screen(attest):
     """Integer data: any stale-LDS race shows as a bitwise mismatch."""
     m = n = 512

@@ -39,10 +39,13 @@ def test_fp8_gemm_integer_exact(attest):
 
 
 def test_fp8_deep_kernel_race_screen(attest):
-    """The deep-pipelined fp8 kernel (M,N%256, K%256): bitwise integer
-    race screen across repeated runs (sync-structure discipline)."""
+    """Production dispatch at a 16-block grid (<= 1 block/CU, K%128)
+    reaches the producer/consumer kernel mfma_gemm_fp8_128pc: bitwise
+    integer race screen of its LDS-flag handoff across repeated runs.
+    (The 8-phase deep kernel is forced variant 1, screened in
+    test_fp8_variants_bitwise.)"""
     m = n = 512
-    k = 768  # K%256 == 0 -> deep kernel; odd nk exercises tail drains
+    k = 768  # nk = 6: both buffers wrap three times
     a = _fp8(torch.randint(-2, 2, (m, k), device="cuda").float())
     bt = _fp8(torch.randint(-2, 2, (n, k), device="cuda").float())
     ref = a.float() @ bt.float().t()
@@ -53,13 +56,7 @@ def test_fp8_deep_kernel_race_screen(attest):
         assert torch.equal(c, ref), f"trial {trial}"
 
 
-@pytest.mark.parametrize("which", [0, 2, 3, 4, 5, 6])
-def test_fp8_variants_bitwise(attest, which):
-    """Every fp8 structure variant (BK=128 / BK=256 / BK=64-hiocc /
-    BK=128 3-blk / BK=128 single-buffered 4-blk / 256x128-tile) must
-    agree bitwise with the fp32 reference on integer data."""
-    m = n = 512
-    k = 1024
+def _variant_bitwise_screen(attest, which, m, n, k):
     torch.manual_seed(which)
     a = _fp8(torch.randint(-2, 2, (m, k), device="cuda").float())
     bt = _fp8(torch.randint(-2, 2, (n, k), device="cuda").float())
@@ -73,8 +70,27 @@ def test_fp8_variants_bitwise(attest, which):
         assert torch.equal(c, ref), f"which={which} trial={trial}"
 
 
-def test_fp8_step3_kernel_still_used_for_small_shapes(attest):
-    """K%256 != 0 routes to the 128-tile step-3 kernel."""
+@pytest.mark.parametrize("which", range(15))
+def test_fp8_variants_bitwise(attest, which):
+    """Every forced fp8 variant (kFp8Variants in attest_kernels.hip: 0-7
+    the structure ladder, 8-12 the option arms of the p/c and 4-blk
+    kernels, 13 the 256-tile 1-blk kernel, 14 split-K) must agree
+    bitwise with the fp32 reference on integer data. Split-K's fp32
+    atomics are exact on this data in any arrival order."""
+    _variant_bitwise_screen(attest, which, 512, 512, 1024)
+
+
+@pytest.mark.parametrize("which", range(15))
+def test_fp8_variants_bitwise_nonsquare(attest, which):
+    """The same screen at m=256, n=512, k=512: 2x4 blocks for the
+    128-tile kernels and 1x2 for the 256-tile ones, so a swapped M/N in
+    the shared epilogue or block mapping shows as a mismatch."""
+    _variant_bitwise_screen(attest, which, 256, 512, 512)
+
+
+def test_fp8_single_block_odd_nk_reaches_pc_kernel(attest):
+    """A one-block grid with K%128 == 0 (nk = 3, odd) also goes to the
+    producer/consumer kernel, not to the step-3 kernel (variant 0)."""
     m, n, k = 128, 128, 384
     a = _fp8(torch.randint(-2, 2, (m, k), device="cuda").float())
     bt = _fp8(torch.randint(-2, 2, (n, k), device="cuda").float())

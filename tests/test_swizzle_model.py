@@ -1,4 +1,4 @@
-"""Python models of the LDS swizzles in ops/attest_kernels.hip, locking
+"""Python models of the LDS swizzles in ops/gemm_common.hip, locking
 the invariants that were enumerated by hand during kernel bring-up
 (docs/KERNELS.md findings 2 and 5). If someone edits a swizzle in the
 .hip file, these tests force the same analysis to be redone.
@@ -11,13 +11,13 @@ each lane reads 16 contiguous bytes.
 
 
 def swz(off: int) -> int:
-    """bf16 3-bit swizzle (attest_kernels.hip:111): row bits 1-3 of the
+    """bf16 3-bit swizzle (gemm_common.hip, swz): row bits 1-3 of the
     128-B-row image into byte bits 4-6."""
     return off ^ (((off >> 8) & 7) << 4)
 
 
 def swz8(off: int) -> int:
-    """fp8 2-bit swizzle (attest_kernels.hip:578): byte bits 5-6 only,
+    """fp8 2-bit swizzle (gemm_common.hip, swz8): byte bits 5-6 only,
     keeping every 32-B fragment contiguous."""
     return off ^ (((off >> 8) & 3) << 5)
 
@@ -105,6 +105,6 @@ def test_fp8_swizzle_residual_conflicts_are_exactly_2way():
 def test_models_match_hip_source():
     """The Python models must stay textually in sync with the .hip
     definitions (cheap tripwire: the exact XOR expressions)."""
-    src = open("k8s_cc_manager_amd/ops/attest_kernels.hip").read()
+    src = open("k8s_cc_manager_amd/ops/gemm_common.hip").read()
     assert "byte_off ^ (((byte_off >> 8) & 7) << 4)" in src  # swz
     assert "byte_off ^ (((byte_off >> 8) & 3) << 5)" in src  # swz8
