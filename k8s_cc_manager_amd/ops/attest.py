@@ -109,6 +109,51 @@ class AttestReport:
         )
 
 
+class _CMxReport(ctypes.Structure):
+    _fields_ = [
+        ("device", ctypes.c_int),
+        ("mx_m", ctypes.c_int),
+        ("mx_n", ctypes.c_int),
+        ("mx_k", ctypes.c_int),
+        ("mx_ms", ctypes.c_double),
+        ("mx_tflops", ctypes.c_double),
+        ("mx_ref_ms", ctypes.c_double),
+        ("mx_max_abs_err", ctypes.c_float),
+        ("mx_checksum", ctypes.c_ulonglong),
+        ("ok", ctypes.c_int),
+        ("error", ctypes.c_char * 256),
+    ]
+
+
+@dataclass
+class MxReport:
+    """Result of the opt-in MXFP4 probe (``attest_mxfp4``)."""
+
+    device: int
+    mx_dim: int
+    mx_ms: float
+    mx_tflops: float
+    mx_ref_ms: float
+    mx_max_abs_err: float
+    mx_checksum: int
+    ok: bool
+    error: str = ""
+
+    @classmethod
+    def from_c(cls, c: _CMxReport) -> "MxReport":
+        special = {
+            "error": c.error.decode(errors="replace"),
+            "mx_dim": c.mx_m,
+            "ok": bool(c.ok),
+        }
+        return cls(
+            **{
+                f.name: special[f.name] if f.name in special else getattr(c, f.name)
+                for f in fields(cls)
+            }
+        )
+
+
 def _load() -> ctypes.CDLL:
     global _lib
     if _lib is not None:
@@ -150,6 +195,19 @@ def _load() -> ctypes.CDLL:
     lib.cc_mfma_gemm_fp8_variant.argtypes = lib.cc_mfma_gemm_bf16.argtypes + [
         ctypes.c_int
     ]
+    lib.cc_mfma_gemm_mxfp4.restype = ctypes.c_int
+    lib.cc_mfma_gemm_mxfp4.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 5 + [
+        ctypes.c_int
+    ] * 3
+    lib.cc_ref_gemm_mxfp4_f32.restype = ctypes.c_int
+    lib.cc_ref_gemm_mxfp4_f32.argtypes = lib.cc_mfma_gemm_mxfp4.argtypes
+    lib.cc_attest_mxfp4.restype = ctypes.c_int
+    lib.cc_attest_mxfp4.argtypes = [
+        ctypes.c_int,
+        ctypes.c_int,
+        ctypes.POINTER(_CMxReport),
+    ]
+    lib.cc_mx_report_sizeof.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -203,6 +261,34 @@ def attest_device(device_index: int, gemm_dim: int = 1024) -> AttestReport:
         rep.xgmi_gbps_max,
     )
     _append_attest_log(rep)
+    return rep
+
+
+def attest_mxfp4(device_index: int, gemm_dim: int = 1024) -> MxReport:
+    """Run the MXFP4 probe on one GPU: the fp4 MFMA GEMM with real E8M0
+    block scales against the VALU reference, bitwise. Raises on failure.
+    gemm_dim below 256 rounds up to 256, otherwise down to a multiple."""
+    lib = _load()
+    c = _CMxReport()
+    rc = lib.cc_attest_mxfp4(device_index, gemm_dim, ctypes.byref(c))
+    rep = MxReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"device {device_index}: mxfp4 probe runtime error rc={rc}: {rep.error}"
+        )
+    if not rep.ok:
+        raise AttestationError(
+            f"device {device_index}: mxfp4 attestation FAILED "
+            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
+        )
+    logger.info(
+        "attested device %d: mxfp4 GEMM %.1f TF/s (%dx%dx%d), bitwise ok",
+        rep.device,
+        rep.mx_tflops,
+        rep.mx_dim,
+        rep.mx_dim,
+        rep.mx_dim,
+    )
     return rep
 
 
@@ -314,6 +400,9 @@ def attest_device_by_bdf(device) -> dict:
 
         deep_attest_device(idx, gemm_dim=gemm_dim)
         deep = True
+    mx = None
+    if os.environ.get("CC_ATTEST_MXFP4", "0") == "1":
+        mx = attest_mxfp4(idx, gemm_dim=gemm_dim)
     summary = {
         "arch": rep.arch.split(":")[0],
         "cus": rep.cu_count,
@@ -329,6 +418,9 @@ def attest_device_by_bdf(device) -> dict:
         ]
     if deep:
         summary["deep_pmc"] = True
+    if mx is not None:
+        summary["mxfp4_tflops"] = round(mx.mx_tflops, 1)
+        summary["mxfp4_bitwise_ok"] = mx.mx_max_abs_err == 0.0
     return summary
 
 
@@ -383,3 +475,22 @@ def mfma_gemm_bf16_variant(device_index: int, a_ptr: int, bt_ptr: int,
     2 = 256x256 8-phase 32x32-op, 3 = 128x128 4-blocks/CU 1-buf."""
     _gemm_call("cc_mfma_gemm_bf16_variant", f"mfma_gemm_bf16_variant({which})",
                device_index, a_ptr, bt_ptr, c_ptr, m, n, k, which)
+
+
+def mfma_gemm_mxfp4(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
+                    sb_ptr: int, c_ptr: int, m: int, n: int, k: int) -> None:
+    """MXFP4 GEMM: C[m,n] = sum over 32-element K blocks kb of
+    2^(SA[m,kb]+SB[n,kb]-254) * sum_k A[m,k]*Bt[n,k], fp32 out. A[M,K]
+    and Bt[N,K] are e2m1 packed two per byte (low nibble = even k), SA
+    and SB uint8 E8M0 [rows, K/32]. M,N multiples of 128, K of 256,
+    16-byte aligned pointers; anything else raises with rc=-2."""
+    _gemm_call("cc_mfma_gemm_mxfp4", "mfma_gemm_mxfp4",
+               device_index, a_ptr, sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k)
+
+
+def ref_gemm_mxfp4_f32(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
+                       sb_ptr: int, c_ptr: int, m: int, n: int, k: int) -> None:
+    """VALU reference of :func:`mfma_gemm_mxfp4` (integer nibble decode,
+    ldexpf scales, no MFMA): any M and N, K a multiple of 32."""
+    _gemm_call("cc_ref_gemm_mxfp4_f32", "ref_gemm_mxfp4_f32",
+               device_index, a_ptr, sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k)

@@ -14,9 +14,12 @@
 //   gemm_fp8.hip       MX-scaled OCP e4m3 MFMA GEMMs (unit e8m0 scales):
 //                      mfma_gemm_fp8_128 / _256 / _128w / _128s / _128t /
 //                      _128u / _256u / _128pc / _256x / _128sk;
+//   gemm_fp4.hip       MXFP4 (e2m1, real e8m0 block scales) MFMA GEMM:
+//                      mfma_gemm_mxfp4_128u;
 //   probe_kernels.hip  fills, ref_gemm_f32 (plain VALU fp32 GEMM of the
 //                      same inputs: the independent on-device ground
-//                      truth), max-diff, checksum, LDS, HBM, liveness.
+//                      truth), the MXFP4 fills and ref_gemm_mxfp4_f32,
+//                      max-diff, checksum, LDS, HBM, liveness.
 //
 // cc_attest_device runs five legs in order:
 //   1. probe_bf16  — production bf16 GEMM dispatch, timed, compared
@@ -30,6 +33,8 @@
 //   5. probe_xgmi  — for every sampled accessible peer: timed copies of
 //                    the result buffer across the link and a checksum
 //                    recomputed ON THE PEER.
+// cc_attest_mxfp4 is a separate, opt-in probe with its own report:
+// the MXFP4 GEMM against ref_gemm_mxfp4_f32, bitwise.
 
 #include <hip/hip_runtime.h>
 
@@ -42,6 +47,7 @@
 #include "gemm_common.hip"
 #include "gemm_bf16.hip"
 #include "gemm_fp8.hip"
+#include "gemm_fp4.hip"
 #include "probe_kernels.hip"
 
 #define CC_CHECK(expr)                                                         \
@@ -275,19 +281,27 @@ struct ProbeCtx {
   // per-probe link sample (full 7-link coverage amortized over
   // consecutive probes instead of per probe)
   int peer_cursor = 0;
+  // MXFP4 leg (cc_attest_mxfp4): lazily allocated like the peer
+  // buffers, so the default probe's context holds nothing of it
+  int mx_dim = 0;
+  int mx_ref_valid = 0;
+  unsigned char *dMxA = nullptr, *dMxB = nullptr;    // packed fp4
+  unsigned char *dMxSA = nullptr, *dMxSB = nullptr;  // e8m0
+  float *dMxC = nullptr, *dMxRef = nullptr, *dMxErr = nullptr;
+  unsigned long long* dMxSum = nullptr;
 };
 
 static ProbeCtx g_ctx[kMaxDevices];
 static std::mutex g_ctx_mu;
 
 // The context's device buffers, in allocation order. bytes == 0: not
-// allocated by ctx_acquire (the peer-leg buffers are lazy).
+// allocated by ctx_acquire (the peer-leg and MXFP4 buffers are lazy).
 struct CtxBuffer {
   void** ptr;
   size_t bytes;
 };
 
-static std::array<CtxBuffer, 13> ctx_buffers(ProbeCtx& c, long elems) {
+static std::array<CtxBuffer, 21> ctx_buffers(ProbeCtx& c, long elems) {
   return {{
       {(void**)&c.dA, elems * sizeof(bf16)},
       {(void**)&c.dB, elems * sizeof(bf16)},
@@ -302,6 +316,14 @@ static std::array<CtxBuffer, 13> ctx_buffers(ProbeCtx& c, long elems) {
       {(void**)&c.dLive, sizeof(int)},
       {(void**)&c.dPeerDst, 0},
       {(void**)&c.dPeerSum, 0},
+      {(void**)&c.dMxA, 0},
+      {(void**)&c.dMxB, 0},
+      {(void**)&c.dMxSA, 0},
+      {(void**)&c.dMxSB, 0},
+      {(void**)&c.dMxC, 0},
+      {(void**)&c.dMxRef, 0},
+      {(void**)&c.dMxErr, 0},
+      {(void**)&c.dMxSum, 0},
   }};
 }
 
@@ -371,7 +393,78 @@ struct CcAttestReport {
   int ok;
 };
 
+// Report of the opt-in MXFP4 probe (cc_attest_mxfp4); CcAttestReport
+// stays as it is.
+struct CcMxReport {
+  int device;
+  int mx_m, mx_n, mx_k;
+  double mx_ms;
+  double mx_tflops;
+  double mx_ref_ms;       // 0.0 when the cached reference was used
+  float mx_max_abs_err;   // MFMA vs VALU reference (must be 0.0)
+  unsigned long long mx_checksum;
+  int ok;
+  char error[256];
+};
+
 }  // extern "C"
+
+// The MXFP4 leg's buffers for dimension D, on top of whatever context
+// the device has (none is needed: the events are created here if the
+// main probe has not run yet).
+static hipError_t mx_acquire(int device, int D, ProbeCtx** out) {
+  ProbeCtx& c = g_ctx[device];
+  *out = &c;
+  hipError_t e;
+  if (!c.ev0 && (e = hipEventCreate(&c.ev0)) != hipSuccess) return e;
+  if (!c.ev1 && (e = hipEventCreate(&c.ev1)) != hipSuccess) return e;
+  if (c.mx_dim == D) return hipSuccess;
+  const size_t elems = (size_t)D * D;
+  const CtxBuffer bufs[] = {
+      {(void**)&c.dMxA, elems / 2},
+      {(void**)&c.dMxB, elems / 2},
+      {(void**)&c.dMxSA, elems / 32},
+      {(void**)&c.dMxSB, elems / 32},
+      {(void**)&c.dMxC, elems * sizeof(float)},
+      {(void**)&c.dMxRef, elems * sizeof(float)},
+      {(void**)&c.dMxErr, sizeof(float)},
+      {(void**)&c.dMxSum, sizeof(unsigned long long)},
+  };
+  c.mx_dim = 0;
+  c.mx_ref_valid = 0;
+  for (const CtxBuffer& b : bufs) {
+    if (*b.ptr) (void)hipFree(*b.ptr);
+    *b.ptr = nullptr;
+    if ((e = hipMalloc(b.ptr, b.bytes)) != hipSuccess) return e;
+  }
+  c.mx_dim = D;
+  return hipSuccess;
+}
+
+// Launch the MXFP4 MFMA GEMM (no sync); -2 for a shape that does not
+// fit the 128x128x256 tile or operands that are not 16-byte aligned
+// (the tile DMA moves 16 B per lane, the scale loads 8 B).
+static int launch_mxfp4(const void* A, const void* SA, const void* Bt,
+                        const void* SB, void* C, int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BK4) return -2;
+  if ((((uintptr_t)A | (uintptr_t)Bt | (uintptr_t)SA | (uintptr_t)SB |
+        (uintptr_t)C) & 15) != 0)
+    return -2;
+  hipLaunchKernelGGL(mfma_gemm_mxfp4_128u, dim3(N / BN, M / BM), dim3(256), 0,
+                     0, (const char*)A, (const unsigned char*)SA,
+                     (const char*)Bt, (const unsigned char*)SB, (float*)C, M,
+                     N, K);
+  return 0;
+}
+
+static void launch_ref_mxfp4(const void* A, const void* SA, const void* Bt,
+                             const void* SB, void* C, int M, int N, int K) {
+  dim3 block(16, 16), grid((N + 15) / 16, (M + 15) / 16);
+  hipLaunchKernelGGL(ref_gemm_mxfp4_f32, grid, block, 0, 0,
+                     (const unsigned char*)A, (const unsigned char*)SA,
+                     (const unsigned char*)Bt, (const unsigned char*)SB,
+                     (float*)C, M, N, K);
+}
 
 // ===========================================================================
 // Probe legs. Each takes the context and the report and returns 0, a
@@ -380,9 +473,8 @@ struct CcAttestReport {
 
 // record, launch, record, sync: the launch's time on the null stream.
 // `launch` returns 0 or a status that aborts the leg.
-template <typename Launch>
-static int timed_ms(ProbeCtx* ctx, CcAttestReport* rep, double* ms,
-                    Launch launch) {
+template <typename Report, typename Launch>
+static int timed_ms(ProbeCtx* ctx, Report* rep, double* ms, Launch launch) {
   hipEvent_t ev0 = ctx->ev0, ev1 = ctx->ev1;
   CC_CHECK(hipEventRecord(ev0, 0));
   CC_TRY(launch());
@@ -617,6 +709,62 @@ static int probe_xgmi(ProbeCtx* ctx, CcAttestReport* rep) {
   return 0;
 }
 
+// MXFP4 leg: all 16 e2m1 codes and scale bytes {126,127,128} through
+// the fp4 decoders and the block-scale hardware, bitwise against the
+// VALU reference (exactness budget at fill_fp4_lcg).
+static int probe_mxfp4(ProbeCtx* ctx, CcMxReport* rep) {
+  const int D = ctx->mx_dim;
+  const long elems = (long)D * D;
+  float *dC = ctx->dMxC, *dErr = ctx->dMxErr;
+  unsigned long long* dSum = ctx->dMxSum;
+  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
+  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
+  // prefill with 0x7f7f7f7f (3.4e38, finite: max_abs_diff's fmaxf would
+  // drop a NaN): an output the kernel never wrote shows as a huge error
+  CC_CHECK(hipMemset(dC, 0x7F, elems * sizeof(float)));
+
+  hipLaunchKernelGGL(fill_fp4_lcg, dim3(2048), dim3(256), 0, 0, ctx->dMxA,
+                     elems / 2, 1u);
+  hipLaunchKernelGGL(fill_fp4_lcg, dim3(2048), dim3(256), 0, 0, ctx->dMxB,
+                     elems / 2, 7u);
+  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, ctx->dMxSA,
+                     elems / 32, 1u);
+  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, ctx->dMxSB,
+                     elems / 32, 7u);
+
+  auto launch = [&] {
+    return launch_mxfp4(ctx->dMxA, ctx->dMxSA, ctx->dMxB, ctx->dMxSB, dC, D, D,
+                        D) != 0
+               ? -6
+               : 0;
+  };
+  CC_TRY(launch());
+  CC_CHECK(hipDeviceSynchronize());
+  CC_TRY(timed_ms(ctx, rep, &rep->mx_ms, launch));
+  rep->mx_tflops = 2.0 * D * (double)D * D / (rep->mx_ms * 1e-3) / 1e12;
+
+  // deterministic fill: the reference is a constant per dim
+  if (!ctx->mx_ref_valid) {
+    CC_TRY(timed_ms(ctx, rep, &rep->mx_ref_ms, [&] {
+      launch_ref_mxfp4(ctx->dMxA, ctx->dMxSA, ctx->dMxB, ctx->dMxSB,
+                       ctx->dMxRef, D, D, D);
+      return 0;
+    }));
+    ctx->mx_ref_valid = 1;
+  } else {
+    rep->mx_ref_ms = 0.0;  // cached
+  }
+
+  hipLaunchKernelGGL(max_abs_diff, dim3(1024), dim3(256), 0, 0, dC,
+                     ctx->dMxRef, elems, dErr);
+  hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0, dC, elems,
+                     dSum);
+  CC_CHECK(hipDeviceSynchronize());
+  CC_CHECK(read_back(dErr, &rep->mx_max_abs_err));
+  CC_CHECK(read_back(dSum, &rep->mx_checksum));
+  return 0;
+}
+
 // ===========================================================================
 // C API
 // ===========================================================================
@@ -750,11 +898,59 @@ int cc_attest_device(int device, int gemm_dim, struct CcAttestReport* rep) {
 // from wrong offsets (checked by a CPU test on every suite run).
 int cc_report_sizeof(void) { return (int)sizeof(struct CcAttestReport); }
 
+// MXFP4 GEMM on caller-provided device buffers (layout in
+// gemm_fp4.hip): packed e2m1 A[M,K/2], Bt[N,K/2], e8m0 SA[M,K/32],
+// SB[N,K/32], fp32 C[M,N]. M,N multiples of 128, K of 256; anything
+// else returns -2 without launching.
+int cc_mfma_gemm_mxfp4(int device, const void* A, const void* SA,
+                       const void* Bt, const void* SB, void* C, int M, int N,
+                       int K) {
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  int rc = launch_mxfp4(A, SA, Bt, SB, C, M, N, K);
+  if (rc != 0) return rc;
+  return (int)hipDeviceSynchronize();
+}
+
+// VALU reference of the same convention: any M and N, K a multiple of 32.
+int cc_ref_gemm_mxfp4_f32(int device, const void* A, const void* SA,
+                          const void* Bt, const void* SB, void* C, int M,
+                          int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0 || K % 32) return -2;
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  launch_ref_mxfp4(A, SA, Bt, SB, C, M, N, K);
+  return (int)hipDeviceSynchronize();
+}
+
+// The opt-in MXFP4 probe. gemm_dim below 256 rounds up to 256, otherwise
+// down to a multiple of 256. rep->ok = 1 iff the MFMA result equals the
+// VALU reference bitwise.
+int cc_attest_mxfp4(int device, int gemm_dim, struct CcMxReport* rep) {
+  if (!rep) return -1;
+  __builtin_memset(rep, 0, sizeof(*rep));
+  rep->device = device;
+  if (device < 0 || device >= kMaxDevices) return -5;
+  CC_CHECK(hipSetDevice(device));
+
+  const int D = gemm_dim < BK4 ? BK4 : (gemm_dim / BK4) * BK4;
+  rep->mx_m = rep->mx_n = rep->mx_k = D;
+
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  ProbeCtx* ctx = nullptr;
+  CC_CHECK(mx_acquire(device, D, &ctx));
+  CC_TRY(probe_mxfp4(ctx, rep));
+
+  rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
+  return 0;
+}
+
+// ABI guard for CcMxReport, as cc_report_sizeof for CcAttestReport.
+int cc_mx_report_sizeof(void) { return (int)sizeof(struct CcMxReport); }
+
 // Free every cached probe context (daemon shutdown / tests).
 void cc_attest_shutdown(void) {
   std::lock_guard<std::mutex> lk(g_ctx_mu);
   for (int i = 0; i < kMaxDevices; ++i) {
-    if (g_ctx[i].dim || g_ctx[i].dLive) {
+    if (g_ctx[i].dim || g_ctx[i].dLive || g_ctx[i].mx_dim || g_ctx[i].ev0) {
       (void)hipSetDevice(i);
       ctx_release(g_ctx[i]);
     }

@@ -58,6 +58,77 @@ __global__ void ref_gemm_f32(const bf16* __restrict__ A,
   C[(long)row * N + col] = acc;
 }
 
+// ---------------------------------------------------------------------------
+// MXFP4 leg: fills and the VALU reference (data convention in
+// gemm_fp4.hip).
+// ---------------------------------------------------------------------------
+// n packed bytes, two e2m1 codes each, all 16 codes. Products are
+// multiples of 2^-2 up to 36; with the scale fill below every term is a
+// multiple of 2^-4 below 2^8, so partial sums up to K = 2048 fit 24
+// bits in any order and the MFMA and VALU paths must agree bitwise.
+__global__ void fill_fp4_lcg(unsigned char* __restrict__ out, long n,
+                             uint32_t seed) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    uint32_t x = (uint32_t)i * 1103515245u + seed * 747796405u + 12345u;
+    x ^= x >> 16;
+    x *= 2654435769u;
+    out[i] = (unsigned char)(x >> 13);
+  }
+}
+
+// E8M0 scale bytes in {126,127,128}: 2^-1, 2^0, 2^1
+__global__ void fill_e8m0_lcg(unsigned char* __restrict__ out, long n,
+                              uint32_t seed) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    uint32_t x = (uint32_t)i * 1103515245u + seed * 747796405u + 12345u;
+    x ^= x >> 16;
+    x *= 2654435769u;
+    out[i] = (unsigned char)(126u + ((x >> 13) % 3u));
+  }
+}
+
+// twice the value of an e2m1 code, as an integer: 0,1,2,3,4,6,8,12
+// with the sign of bit 3 (no hardware conversion instruction)
+__device__ __forceinline__ int e2m1_times2(int code) {
+  int e = (code >> 1) & 3, m = code & 1;
+  int v = e ? (2 + m) << (e - 1) : m;
+  return (code & 8) ? -v : v;
+}
+
+// VALU MXFP4 reference GEMM: one thread per C element; per 32-element
+// block the products are summed in fp32 in k order, the block sum is
+// scaled with ldexpf, and blocks are added in kb order.
+__global__ void ref_gemm_mxfp4_f32(const unsigned char* __restrict__ A,
+                                   const unsigned char* __restrict__ SA,
+                                   const unsigned char* __restrict__ Bt,
+                                   const unsigned char* __restrict__ SB,
+                                   float* __restrict__ C, int M, int N,
+                                   int K) {
+  int col = blockIdx.x * blockDim.x + threadIdx.x;
+  int row = blockIdx.y * blockDim.y + threadIdx.y;
+  if (row >= M || col >= N) return;
+  const unsigned char* a = A + (long)row * (K >> 1);
+  const unsigned char* b = Bt + (long)col * (K >> 1);
+  const unsigned char* sa = SA + (long)row * (K >> 5);
+  const unsigned char* sb = SB + (long)col * (K >> 5);
+  float acc = 0.f;
+  for (int kb = 0; kb < (K >> 5); ++kb) {
+    float blk = 0.f;
+    for (int j = 0; j < 16; ++j) {
+      int ab = a[kb * 16 + j], bb = b[kb * 16 + j];
+      blk += (float)(e2m1_times2(ab & 15) * e2m1_times2(bb & 15));
+      blk += (float)(e2m1_times2(ab >> 4) * e2m1_times2(bb >> 4));
+    }
+    // blk holds 4x the block's dot product
+    acc += ldexpf(blk, (int)sa[kb] + (int)sb[kb] - 254 - 2);
+  }
+  C[(long)row * N + col] = acc;
+}
+
 // max |x-y| reduction over n elements -> out[0] (pre-zeroed)
 __global__ void max_abs_diff(const float* __restrict__ x,
                              const float* __restrict__ y, long n,
