@@ -3,7 +3,8 @@
 One JSON document answering the first questions an operator asks on a
 misbehaving CC node: can the host do TEE at all, is KFD alive, what do
 PCI and amdsmi each see, does the attestation library load, and (with
-``--attest``) does a full probe pass. Every section degrades gracefully
+``--attest``) does a full probe pass (``--cu-sweep`` adds the
+compute-unit sweep, per XCC). Every section degrades gracefully
 — a CPU-only box reports absence, not a stack trace.
 """
 
@@ -17,7 +18,33 @@ from typing import Any, Dict
 from .core.hostprobe import is_host_cc_enabled
 
 
-def collect(run_attest: bool = False, gemm_dim: int = 512) -> Dict[str, Any]:
+def _cu_sweep_section(attest, device_index: int) -> Dict[str, Any]:
+    """The compute-unit sweep of one GPU, with one line per XCC: CUs the
+    sweep reached there and CUs with a failing SIMD."""
+    rep = attest.cu_sweep_report(device_index)
+    seen: Dict[int, set] = {}
+    for key in attest.cu_sweep_units(device_index):
+        seen.setdefault(key >> 10, set()).add(key >> 2)
+    failed: Dict[int, set] = {}
+    for unit in rep.failed_units:
+        failed.setdefault(unit[0], set()).add(unit[:4])
+    return {
+        "device": device_index,
+        "ok": rep.ok,
+        "units": f"{rep.units_seen}/{rep.units_expected}",
+        "launches": rep.launches,
+        "sweep_ms": rep.sweep_ms,
+        "error": rep.error,
+        "failed_units": [attest.unit_name(u) for u in rep.failed_units],
+        "per_xcc": [
+            f"xcc{x}: {len(cus)} CUs seen, {len(failed.get(x, ()))} failed"
+            for x, cus in sorted(seen.items())
+        ],
+    }
+
+
+def collect(run_attest: bool = False, gemm_dim: int = 512,
+            cu_sweep: bool = False) -> Dict[str, Any]:
     report: Dict[str, Any] = {"schema": "cc-doctor/v1"}
 
     # host TEE capability
@@ -104,6 +131,11 @@ def collect(run_attest: bool = False, gemm_dim: int = 512) -> Dict[str, Any]:
                 rep = attest.attest_device(i, gemm_dim=gemm_dim)
                 reports.append(dataclasses.asdict(rep))
             att["probes"] = reports
+            if cu_sweep:
+                att["cu_sweep"] = [
+                    _cu_sweep_section(attest, i)
+                    for i in range(att["hip_device_count"])
+                ]
     except Exception as e:
         att["error"] = str(e)
     report["attestation"] = att
@@ -160,6 +192,10 @@ def main(argv=None) -> int:
     ap.add_argument("--attest", action="store_true",
                     help="run the full attestation probe on every GPU")
     ap.add_argument("--gemm-dim", type=int, default=512)
+    ap.add_argument("--cu-sweep", action="store_true",
+                    help="with --attest: also run the compute-unit sweep "
+                    "(every SIMD of every CU) and list CUs seen and failed "
+                    "per XCC")
     ap.add_argument(
         "--verify-attest-log",
         metavar="PATH",
@@ -178,7 +214,8 @@ def main(argv=None) -> int:
             return 1
         print(json.dumps({"verified": True, "records": n}))
         return 0
-    report = collect(run_attest=args.attest, gemm_dim=args.gemm_dim)
+    report = collect(run_attest=args.attest, gemm_dim=args.gemm_dim,
+                     cu_sweep=args.cu_sweep)
     print(json.dumps(report, indent=2))
     return 0 if report["verdict"]["cc_capable"] or not args.attest else 1
 

@@ -154,6 +154,94 @@ class MxReport:
         )
 
 
+class _CSweepReport(ctypes.Structure):
+    _fields_ = [
+        ("device", ctypes.c_int),
+        ("cu_count", ctypes.c_int),
+        ("units_expected", ctypes.c_int),
+        ("units_seen", ctypes.c_int),
+        ("cus_seen", ctypes.c_int),
+        ("xccs_seen", ctypes.c_int),
+        ("units_failed", ctypes.c_int),
+        ("mfma_failures", ctypes.c_uint),
+        ("lds_failures", ctypes.c_uint),
+        ("launches", ctypes.c_int),
+        ("rounds", ctypes.c_int),
+        ("sweep_ms", ctypes.c_double),
+        ("gold_ms", ctypes.c_double),
+        ("failed_keys", ctypes.c_uint * 16),
+        ("ok", ctypes.c_int),
+        ("error", ctypes.c_char * 256),
+    ]
+
+
+SWEEP_GOLD_ELEMS = 3328  # floats in the sweep's four golden C images
+
+
+# Unit key of the compute-unit sweep (ops/cu_sweep.hip):
+# XCC_ID[3:0] << 10 | HW_ID[15:8] << 2 | SIMD_ID, with HW_ID's CU_ID in
+# bits 11:8, SH_ID in bit 12, SE_ID in bits 14:13.
+
+def encode_unit(xcc: int, se: int, sh: int, cu: int, simd: int) -> int:
+    """(xcc, se, sh, cu, simd) -> the sweep's 14-bit unit key."""
+    for name, value, limit in (("xcc", xcc, 16), ("se", se, 4), ("sh", sh, 2),
+                               ("cu", cu, 16), ("simd", simd, 4)):
+        if not 0 <= value < limit:
+            raise ValueError(f"{name}={value} outside 0..{limit - 1}")
+    return (xcc << 10) | (se << 7) | (sh << 6) | (cu << 2) | simd
+
+
+def decode_unit(key: int) -> tuple:
+    """Unit key -> (xcc, se, sh, cu, simd). Bit 9 of the key (HW_ID bit
+    15, above the documented SE_ID field) is not part of the tuple."""
+    return (
+        (key >> 10) & 15,
+        (key >> 7) & 3,
+        (key >> 6) & 1,
+        (key >> 2) & 15,
+        key & 3,
+    )
+
+
+@dataclass
+class CuSweepReport:
+    """Result of the opt-in compute-unit sweep (``sweep_compute_units``).
+    A unit is one SIMD of one CU; ``failed_units`` holds the first 16
+    that miscompared, decoded to (xcc, se, sh, cu, simd)."""
+
+    device: int
+    cu_count: int
+    units_expected: int
+    units_seen: int
+    cus_seen: int
+    xccs_seen: int
+    units_failed: int
+    mfma_failures: int
+    lds_failures: int
+    launches: int
+    rounds: int
+    sweep_ms: float
+    gold_ms: float
+    failed_units: list
+    ok: bool
+    error: str = ""
+
+    @classmethod
+    def from_c(cls, c: _CSweepReport) -> "CuSweepReport":
+        n = max(0, min(c.units_failed, len(c.failed_keys)))
+        special = {
+            "error": c.error.decode(errors="replace"),
+            "failed_units": [decode_unit(c.failed_keys[i]) for i in range(n)],
+            "ok": bool(c.ok),
+        }
+        return cls(
+            **{
+                f.name: special[f.name] if f.name in special else getattr(c, f.name)
+                for f in fields(cls)
+            }
+        )
+
+
 def _load() -> ctypes.CDLL:
     global _lib
     if _lib is not None:
@@ -208,6 +296,23 @@ def _load() -> ctypes.CDLL:
         ctypes.POINTER(_CMxReport),
     ]
     lib.cc_mx_report_sizeof.restype = ctypes.c_int
+    lib.cc_cu_sweep.restype = ctypes.c_int
+    lib.cc_cu_sweep.argtypes = [
+        ctypes.c_int,
+        ctypes.c_int,
+        ctypes.c_int,
+        ctypes.POINTER(_CSweepReport),
+    ]
+    lib.cc_cu_sweep_gold.restype = ctypes.c_int
+    lib.cc_cu_sweep_gold.argtypes = [
+        ctypes.c_int,
+        ctypes.c_int,
+        ctypes.POINTER(ctypes.c_float),
+    ]
+    for fn in (lib.cc_cu_sweep_units, lib.cc_cu_sweep_hits):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint), ctypes.c_int]
+    lib.cc_sweep_report_sizeof.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -290,6 +395,102 @@ def attest_mxfp4(device_index: int, gemm_dim: int = 1024) -> MxReport:
         rep.mx_dim,
     )
     return rep
+
+
+CU_SWEEP_MAX_ROUNDS = 256  # exactness cap of the sweep's MFMA chains
+
+
+def unit_name(unit: tuple) -> str:
+    return "xcc%d/se%d/sh%d/cu%d/simd%d" % unit
+
+
+def cu_sweep_report(device_index: int, rounds: int = 32,
+                    _poison_key: int = -1) -> CuSweepReport:
+    """Run the compute-unit sweep and return its report whatever it
+    found; raises only when the sweep itself could not run (rc != 0,
+    e.g. rc=-2 for ``rounds`` outside 1..CU_SWEEP_MAX_ROUNDS)."""
+    lib = _load()
+    c = _CSweepReport()
+    rc = lib.cc_cu_sweep(device_index, rounds, _poison_key, ctypes.byref(c))
+    rep = CuSweepReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"device {device_index}: cu sweep runtime error: {rep.error} rc={rc}"
+        )
+    return rep
+
+
+def sweep_compute_units(device_index: int, rounds: int = 32,
+                        _poison_key: int = -1) -> CuSweepReport:
+    """Run the matrix-core and whole-LDS self-test on every SIMD of every
+    CU of one GPU: four MFMA chains of ``rounds`` accumulating
+    instructions per wave (bf16 32x32x16 and 16x16x32, block-scaled e4m3
+    and e2m1 32x32x64) compared bitwise with a VALU reference, an LDS
+    march over all 160 KiB, and the unit each wave ran on read from the
+    hardware ID registers. Raises when a unit miscompares or when a unit
+    was never reached. ``_poison_key`` makes the waves of that unit
+    produce one wrong number (for testing the detector)."""
+    rep = cu_sweep_report(device_index, rounds, _poison_key)
+    if not rep.ok:
+        if rep.units_failed or rep.lds_failures:
+            units = ", ".join(unit_name(u) for u in rep.failed_units)
+            more = rep.units_failed - len(rep.failed_units)
+            raise AttestationError(
+                f"device {device_index}: cu sweep FAILED on {rep.units_failed} "
+                f"unit(s): {units}{f' and {more} more' if more > 0 else ''} "
+                f"(mfma_failures={rep.mfma_failures}, "
+                f"lds_failures={rep.lds_failures})"
+            )
+        raise AttestationError(
+            f"device {device_index}: cu sweep FAILED: {rep.error} "
+            f"({rep.cus_seen}/{rep.cu_count} CUs)"
+        )
+    logger.info(
+        "attested device %d: cu sweep %d/%d units on %d CUs of %d XCCs, "
+        "%d launch(es), %.2f ms",
+        rep.device,
+        rep.units_seen,
+        rep.units_expected,
+        rep.cus_seen,
+        rep.xccs_seen,
+        rep.launches,
+        rep.sweep_ms,
+    )
+    return rep
+
+
+def cu_sweep_gold(device_index: int, rounds: int) -> list:
+    """The sweep's golden C images for ``rounds`` from the VALU reference
+    kernel: 3328 floats, row-major 32x32 (bf16 32x32x16), 16x16 (bf16
+    16x16x32), 32x32 (e4m3) and 32x32 (e2m1)."""
+    buf = (ctypes.c_float * SWEEP_GOLD_ELEMS)()
+    rc = _load().cc_cu_sweep_gold(device_index, rounds, buf)
+    if rc != 0:
+        raise AttestationError(f"cu_sweep_gold rc={rc}")
+    return list(buf)
+
+
+def _cu_sweep_table(fn_name: str, device_index: int) -> list:
+    fn = getattr(_load(), fn_name)
+    n = fn(device_index, None, 0)
+    if n < 0:
+        raise AttestationError(f"{fn_name} rc={n}")
+    buf = (ctypes.c_uint * max(n, 1))()
+    n = min(n, fn(device_index, buf, n))
+    return [int(buf[i]) for i in range(n)]
+
+
+def cu_sweep_units(device_index: int) -> list:
+    """Keys of the units the last sweep on this device reached,
+    ascending (``decode_unit`` names them)."""
+    return _cu_sweep_table("cc_cu_sweep_units", device_index)
+
+
+def cu_sweep_hits(device_index: int) -> dict:
+    """Unit key -> number of waves that reported from it in the last
+    sweep on this device."""
+    return dict(zip(cu_sweep_units(device_index),
+                    _cu_sweep_table("cc_cu_sweep_hits", device_index)))
 
 
 _GENESIS = "cc-attest-log-v1"
@@ -403,6 +604,9 @@ def attest_device_by_bdf(device) -> dict:
     mx = None
     if os.environ.get("CC_ATTEST_MXFP4", "0") == "1":
         mx = attest_mxfp4(idx, gemm_dim=gemm_dim)
+    sweep = None
+    if os.environ.get("CC_ATTEST_CU_SWEEP", "0") == "1":
+        sweep = sweep_compute_units(idx)
     summary = {
         "arch": rep.arch.split(":")[0],
         "cus": rep.cu_count,
@@ -421,6 +625,9 @@ def attest_device_by_bdf(device) -> dict:
     if mx is not None:
         summary["mxfp4_tflops"] = round(mx.mx_tflops, 1)
         summary["mxfp4_bitwise_ok"] = mx.mx_max_abs_err == 0.0
+    if sweep is not None:
+        summary["cu_sweep"] = f"{sweep.units_seen}/{sweep.units_expected}"
+        summary["cu_sweep_ok"] = sweep.ok
     return summary
 
 

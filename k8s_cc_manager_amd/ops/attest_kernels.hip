@@ -19,7 +19,10 @@
 //   probe_kernels.hip  fills, ref_gemm_f32 (plain VALU fp32 GEMM of the
 //                      same inputs: the independent on-device ground
 //                      truth), the MXFP4 fills and ref_gemm_mxfp4_f32,
-//                      max-diff, checksum, LDS, HBM, liveness.
+//                      max-diff, checksum, LDS, HBM, liveness;
+//   cu_sweep.hip       compute-unit sweep: cu_sweep (per-SIMD MFMA chains
+//                      and a whole-LDS march, keyed by the hardware ID
+//                      registers) and cu_sweep_gold (its VALU reference).
 //
 // cc_attest_device runs five legs in order:
 //   1. probe_bf16  — production bf16 GEMM dispatch, timed, compared
@@ -35,6 +38,9 @@
 //                    recomputed ON THE PEER.
 // cc_attest_mxfp4 is a separate, opt-in probe with its own report:
 // the MXFP4 GEMM against ref_gemm_mxfp4_f32, bitwise.
+// cc_cu_sweep is another: cu_sweep.hip's matrix-core and whole-LDS
+// self-test on every SIMD of every CU, with the units it reached read
+// from the hardware ID registers.
 
 #include <hip/hip_runtime.h>
 
@@ -49,6 +55,7 @@
 #include "gemm_fp8.hip"
 #include "gemm_fp4.hip"
 #include "probe_kernels.hip"
+#include "cu_sweep.hip"
 
 #define CC_CHECK(expr)                                                         \
   do {                                                                         \
@@ -289,6 +296,13 @@ struct ProbeCtx {
   unsigned char *dMxSA = nullptr, *dMxSB = nullptr;  // e8m0
   float *dMxC = nullptr, *dMxRef = nullptr, *dMxErr = nullptr;
   unsigned long long* dMxSum = nullptr;
+  // compute-unit sweep (cc_cu_sweep): lazily allocated too. hSweepTab
+  // is the host copy of the unit table after the last sweep.
+  unsigned* dSweepTab = nullptr;
+  float* dSweepGold = nullptr;
+  int sweep_gold_rounds = 0;  // rounds dSweepGold was computed for
+  unsigned* hSweepTab = nullptr;
+  int sweep_valid = 0;  // hSweepTab holds a finished sweep
 };
 
 static ProbeCtx g_ctx[kMaxDevices];
@@ -301,7 +315,7 @@ struct CtxBuffer {
   size_t bytes;
 };
 
-static std::array<CtxBuffer, 21> ctx_buffers(ProbeCtx& c, long elems) {
+static std::array<CtxBuffer, 23> ctx_buffers(ProbeCtx& c, long elems) {
   return {{
       {(void**)&c.dA, elems * sizeof(bf16)},
       {(void**)&c.dB, elems * sizeof(bf16)},
@@ -324,12 +338,15 @@ static std::array<CtxBuffer, 21> ctx_buffers(ProbeCtx& c, long elems) {
       {(void**)&c.dMxRef, 0},
       {(void**)&c.dMxErr, 0},
       {(void**)&c.dMxSum, 0},
+      {(void**)&c.dSweepTab, 0},
+      {(void**)&c.dSweepGold, 0},
   }};
 }
 
 static void ctx_release(ProbeCtx& c) {
   for (const CtxBuffer& b : ctx_buffers(c, 0))
     if (*b.ptr) (void)hipFree(*b.ptr);
+  free(c.hSweepTab);
   if (c.ev0) (void)hipEventDestroy(c.ev0);
   if (c.ev1) (void)hipEventDestroy(c.ev1);
   c = ProbeCtx{};
@@ -403,6 +420,20 @@ struct CcMxReport {
   double mx_ref_ms;       // 0.0 when the cached reference was used
   float mx_max_abs_err;   // MFMA vs VALU reference (must be 0.0)
   unsigned long long mx_checksum;
+  int ok;
+  char error[256];
+};
+
+// Report of the opt-in compute-unit sweep (cc_cu_sweep). A unit is one
+// SIMD of one CU, named by the 14-bit key of cu_sweep.hip.
+struct CcSweepReport {
+  int device, cu_count, units_expected, units_seen, cus_seen, xccs_seen;
+  int units_failed;
+  unsigned mfma_failures, lds_failures;
+  int launches, rounds;
+  double sweep_ms;           // device events, all launches
+  double gold_ms;            // 0.0 when cached
+  unsigned failed_keys[16];  // first 16
   int ok;
   char error[256];
 };
@@ -765,6 +796,94 @@ static int probe_mxfp4(ProbeCtx* ctx, CcMxReport* rep) {
   return 0;
 }
 
+// The sweep's buffers, on top of whatever context the device has (as
+// mx_acquire).
+static hipError_t sweep_acquire(int device, ProbeCtx** out) {
+  ProbeCtx& c = g_ctx[device];
+  *out = &c;
+  hipError_t e;
+  if (!c.ev0 && (e = hipEventCreate(&c.ev0)) != hipSuccess) return e;
+  if (!c.ev1 && (e = hipEventCreate(&c.ev1)) != hipSuccess) return e;
+  const size_t tab_b = (size_t)CU_SWEEP_UNITS * CU_SWEEP_REC * sizeof(unsigned);
+  if (!c.dSweepTab && (e = hipMalloc(&c.dSweepTab, tab_b)) != hipSuccess)
+    return e;
+  if (!c.dSweepGold &&
+      (e = hipMalloc(&c.dSweepGold, CU_SWEEP_GOLD_ELEMS * sizeof(float))) !=
+          hipSuccess)
+    return e;
+  if (!c.hSweepTab && !(c.hSweepTab = (unsigned*)calloc(1, tab_b)))
+    return hipErrorOutOfMemory;
+  return hipSuccess;
+}
+
+// The golden C images for `rounds`, a constant: computed once per
+// (device, rounds). *ms = 0.0 when the cached images were used.
+static int sweep_gold(ProbeCtx* ctx, CcSweepReport* rep, int rounds,
+                      double* ms) {
+  *ms = 0.0;
+  if (ctx->sweep_gold_rounds == rounds) return 0;
+  ctx->sweep_gold_rounds = 0;
+  CC_TRY(timed_ms(ctx, rep, ms, [&] {
+    hipLaunchKernelGGL(cu_sweep_gold, dim3(1), dim3(1024), 0, 0,
+                       ctx->dSweepGold, rounds);
+    return 0;
+  }));
+  CC_CHECK(hipGetLastError());
+  ctx->sweep_gold_rounds = rounds;
+  return 0;
+}
+
+static int sweep_units_seen(const unsigned* tab) {
+  int n = 0;
+  for (int k = 0; k < CU_SWEEP_UNITS; ++k) n += tab[k * CU_SWEEP_REC] != 0;
+  return n;
+}
+
+// Sweep leg: up to 4 launches of 4 blocks per CU into one unit table,
+// until every SIMD of every CU has reported.
+static int probe_cu_sweep(ProbeCtx* ctx, CcSweepReport* rep, int poison_key) {
+  const size_t tab_b = (size_t)CU_SWEEP_UNITS * CU_SWEEP_REC * sizeof(unsigned);
+  unsigned* tab = ctx->hSweepTab;
+  CC_TRY(sweep_gold(ctx, rep, rep->rounds, &rep->gold_ms));
+  ctx->sweep_valid = 0;
+  CC_CHECK(hipMemset(ctx->dSweepTab, 0, tab_b));
+  const int kMaxLaunches = 4;
+  for (int l = 0; l < kMaxLaunches; ++l) {
+    double ms = 0.0;
+    CC_TRY(timed_ms(ctx, rep, &ms, [&] {
+      hipLaunchKernelGGL(cu_sweep, dim3(4 * rep->cu_count), dim3(1024), 0, 0,
+                         ctx->dSweepGold, ctx->dSweepTab, rep->rounds,
+                         poison_key);
+      return 0;
+    }));
+    CC_CHECK(hipGetLastError());
+    rep->sweep_ms += ms;
+    rep->launches = l + 1;
+    CC_CHECK(hipMemcpy(tab, ctx->dSweepTab, tab_b, hipMemcpyDeviceToHost));
+    if (sweep_units_seen(tab) >= rep->units_expected) break;
+  }
+  ctx->sweep_valid = 1;
+
+  unsigned long long xccs = 0;
+  int last_cu = -1;  // keys ascend, a CU's four SIMDs are adjacent
+  for (int k = 0; k < CU_SWEEP_UNITS; ++k) {
+    const unsigned* rec = tab + k * CU_SWEEP_REC;
+    if (!rec[0]) continue;
+    ++rep->units_seen;
+    if ((k >> 2) != last_cu) ++rep->cus_seen;
+    last_cu = k >> 2;
+    xccs |= 1ull << (k >> 10);
+    rep->mfma_failures += rec[1];
+    rep->lds_failures += rec[2];
+    if (rec[1] || rec[2]) {
+      if (rep->units_failed < 16) rep->failed_keys[rep->units_failed] = k;
+      ++rep->units_failed;
+    }
+  }
+  rep->xccs_seen = __builtin_popcountll(xccs);
+  return 0;
+}
+
 // ===========================================================================
 // C API
 // ===========================================================================
@@ -945,6 +1064,99 @@ int cc_attest_mxfp4(int device, int gemm_dim, struct CcMxReport* rep) {
 
 // ABI guard for CcMxReport, as cc_report_sizeof for CcAttestReport.
 int cc_mx_report_sizeof(void) { return (int)sizeof(struct CcMxReport); }
+
+// The opt-in compute-unit sweep. rounds: accumulating MFMAs per chain,
+// 1..CU_SWEEP_MAX_ROUNDS (anything else returns -2 without launching).
+// poison_key: -1, or the key of a unit whose waves flip one accumulator
+// bit before the compare (a wrong number, to test the detector).
+// rep->ok = 1 iff no unit miscompared and every SIMD of every CU
+// reported; short coverage is a failure with rep->error set.
+int cc_cu_sweep(int device, int rounds, int poison_key,
+                struct CcSweepReport* rep) {
+  if (!rep) return -1;
+  __builtin_memset(rep, 0, sizeof(*rep));
+  rep->device = device;
+  rep->rounds = rounds;
+  if (device < 0 || device >= kMaxDevices) return -5;
+  if (rounds < 1 || rounds > CU_SWEEP_MAX_ROUNDS) {
+    snprintf(rep->error, sizeof(rep->error), "rounds %d outside 1..%d", rounds,
+             CU_SWEEP_MAX_ROUNDS);
+    return -2;
+  }
+  CC_CHECK(hipSetDevice(device));
+  hipDeviceProp_t prop;
+  CC_CHECK(hipGetDeviceProperties(&prop, device));
+  rep->cu_count = prop.multiProcessorCount;
+  rep->units_expected = 4 * rep->cu_count;
+
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  ProbeCtx* ctx = nullptr;
+  CC_CHECK(sweep_acquire(device, &ctx));
+  CC_TRY(probe_cu_sweep(ctx, rep, poison_key));
+
+  const bool covered = rep->units_seen == rep->units_expected &&
+                       rep->cus_seen == rep->cu_count;
+  if (!covered)
+    snprintf(rep->error, sizeof(rep->error),
+             "coverage %d/%d after %d launches", rep->units_seen,
+             rep->units_expected, rep->launches);
+  rep->ok = covered && rep->units_failed == 0 && rep->lds_failures == 0 ? 1 : 0;
+  return 0;
+}
+
+// The golden C images of the sweep for `rounds` (3328 floats: 32x32,
+// 16x16, 32x32, 32x32, row-major), copied to the host.
+int cc_cu_sweep_gold(int device, int rounds, float* host_out_3328) {
+  if (!host_out_3328) return -1;
+  if (device < 0 || device >= kMaxDevices) return -5;
+  if (rounds < 1 || rounds > CU_SWEEP_MAX_ROUNDS) return -2;
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  ProbeCtx* ctx = nullptr;
+  if (sweep_acquire(device, &ctx) != hipSuccess) return -4;
+  CcSweepReport scratch;
+  double ms = 0.0;
+  CC_TRY(sweep_gold(ctx, &scratch, rounds, &ms));
+  return (int)hipMemcpy(host_out_3328, ctx->dSweepGold,
+                        CU_SWEEP_GOLD_ELEMS * sizeof(float),
+                        hipMemcpyDeviceToHost);
+}
+
+// Keys of the units the last sweep on `device` reached, ascending, at
+// most `cap` of them written; returns how many there are (0 before the
+// first sweep).
+int cc_cu_sweep_units(int device, unsigned* keys_out, int cap) {
+  if (device < 0 || device >= kMaxDevices) return -5;
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  const ProbeCtx& c = g_ctx[device];
+  if (!c.sweep_valid) return 0;
+  int n = 0;
+  for (int k = 0; k < CU_SWEEP_UNITS; ++k) {
+    if (!c.hSweepTab[k * CU_SWEEP_REC]) continue;
+    if (keys_out && n < cap) keys_out[n] = (unsigned)k;
+    ++n;
+  }
+  return n;
+}
+
+// How many waves reported from each of those units, in the same order.
+int cc_cu_sweep_hits(int device, unsigned* hits_out, int cap) {
+  if (device < 0 || device >= kMaxDevices) return -5;
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  const ProbeCtx& c = g_ctx[device];
+  if (!c.sweep_valid) return 0;
+  int n = 0;
+  for (int k = 0; k < CU_SWEEP_UNITS; ++k) {
+    unsigned hits = c.hSweepTab[k * CU_SWEEP_REC];
+    if (!hits) continue;
+    if (hits_out && n < cap) hits_out[n] = hits;
+    ++n;
+  }
+  return n;
+}
+
+// ABI guard for CcSweepReport, as cc_report_sizeof for CcAttestReport.
+int cc_sweep_report_sizeof(void) { return (int)sizeof(struct CcSweepReport); }
 
 // Free every cached probe context (daemon shutdown / tests).
 void cc_attest_shutdown(void) {
