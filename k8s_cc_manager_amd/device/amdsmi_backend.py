@@ -230,7 +230,7 @@ class AmdSmiDevice(CCDevice):
                     from ..ops import attest
 
                     try:
-                        lib = attest._load()
+                        rc = attest.device_alive(self.hip_index)
                     except attest.AttestationError as e:
                         # degrade LOUDLY: an amdsmi answer alone is a far
                         # weaker boot gate than the documented "kernel
@@ -243,7 +243,6 @@ class AmdSmiDevice(CCDevice):
                             e,
                         )
                         return
-                    rc = lib.cc_device_alive(self.hip_index)
                     if rc != 0:
                         last_err = f"liveness kernel rc={rc}"
                         time.sleep(0.2)
@@ -324,8 +323,7 @@ def _hip_index_by_bdf() -> Dict[str, int]:
     try:
         from ..ops import attest
 
-        lib = attest._load()
-        n = lib.cc_device_count()
+        n = attest.device_count()
     except Exception:
         return out
     # invert by probing each sysfs AMD GPU bdf through the C helper
@@ -334,11 +332,11 @@ def _hip_index_by_bdf() -> Dict[str, int]:
 
         for entry in pci_scan():
             bdf = entry["bdf"]
-            dom, rest = bdf.split(":", 1)
-            bus, devfn = rest.split(":")
-            dev, _fn = devfn.split(".")
-            idx = lib.cc_device_index_for_bdf(int(dom, 16), int(bus, 16), int(dev, 16))
-            if 0 <= idx < n:
+            try:
+                idx = attest.device_index_for_bdf(bdf)
+            except attest.AttestationError:
+                continue  # no HIP device at this bdf
+            if idx < n:
                 out[bdf] = idx
     except Exception as e:  # pragma: no cover
         logger.debug("hip index mapping unavailable: %s", e)

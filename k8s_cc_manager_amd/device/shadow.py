@@ -89,10 +89,9 @@ class ShadowHipDevice(CCDevice):
         from ..ops import attest
 
         try:
-            lib = attest._load()
+            rc = attest.device_alive(self.hip_index)
         except attest.AttestationError as e:
             raise CCDeviceError(str(e)) from e
-        rc = lib.cc_device_alive(self.hip_index)
         if rc != 0:
             raise BootTimeoutError(
                 f"{self.bdf}: liveness kernel failed on HIP device "
@@ -110,8 +109,7 @@ class ShadowBackend(DeviceBackend):
     def __init__(self, device_indices: Optional[List[int]] = None):
         from ..ops import attest
 
-        lib = attest._load()
-        n = lib.cc_device_count()
+        n = attest.device_count()
         if n <= 0:
             raise CCDeviceError("no HIP devices visible")
         indices = device_indices if device_indices is not None else list(range(n))

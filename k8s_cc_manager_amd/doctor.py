@@ -120,9 +120,9 @@ def collect(run_attest: bool = False, gemm_dim: int = 512,
     try:
         from .ops import attest
 
-        attest._load()
+        count = attest.device_count()  # raises when the library is missing
         att["library_loaded"] = True
-        att["hip_device_count"] = attest.device_count()
+        att["hip_device_count"] = count
         if run_attest and att["hip_device_count"] > 0:
             import dataclasses
 

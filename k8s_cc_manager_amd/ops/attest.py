@@ -28,6 +28,15 @@ class AttestationError(Exception):
     labeled ready."""
 
 
+def _from_c(cls, c, **special):
+    """Build report dataclass ``cls`` from its C mirror: every same-named
+    field is copied, ``error`` decoded and ``ok`` made a bool; ``special``
+    holds the fields whose Python form differs."""
+    special.update(error=c.error.decode(errors="replace"), ok=bool(c.ok))
+    return cls(**{f.name: special[f.name] if f.name in special
+                  else getattr(c, f.name) for f in fields(cls)})
+
+
 class _CReport(ctypes.Structure):
     _fields_ = [
         ("device", ctypes.c_int),
@@ -93,20 +102,8 @@ class AttestReport:
 
     @classmethod
     def from_c(cls, c: _CReport) -> "AttestReport":
-        """Copy every same-named field of the C report; only the fields
-        whose Python form differs are spelled out."""
-        special = {
-            "arch": c.arch.decode(errors="replace"),
-            "error": c.error.decode(errors="replace"),
-            "gemm_dim": c.gemm_m,
-            "ok": bool(c.ok),
-        }
-        return cls(
-            **{
-                f.name: special[f.name] if f.name in special else getattr(c, f.name)
-                for f in fields(cls)
-            }
-        )
+        return _from_c(cls, c, arch=c.arch.decode(errors="replace"),
+                       gemm_dim=c.gemm_m)
 
 
 class _CMxReport(ctypes.Structure):
@@ -141,17 +138,7 @@ class MxReport:
 
     @classmethod
     def from_c(cls, c: _CMxReport) -> "MxReport":
-        special = {
-            "error": c.error.decode(errors="replace"),
-            "mx_dim": c.mx_m,
-            "ok": bool(c.ok),
-        }
-        return cls(
-            **{
-                f.name: special[f.name] if f.name in special else getattr(c, f.name)
-                for f in fields(cls)
-            }
-        )
+        return _from_c(cls, c, mx_dim=c.mx_m)
 
 
 class _CSweepReport(ctypes.Structure):
@@ -229,17 +216,38 @@ class CuSweepReport:
     @classmethod
     def from_c(cls, c: _CSweepReport) -> "CuSweepReport":
         n = max(0, min(c.units_failed, len(c.failed_keys)))
-        special = {
-            "error": c.error.decode(errors="replace"),
-            "failed_units": [decode_unit(c.failed_keys[i]) for i in range(n)],
-            "ok": bool(c.ok),
-        }
-        return cls(
-            **{
-                f.name: special[f.name] if f.name in special else getattr(c, f.name)
-                for f in fields(cls)
-            }
-        )
+        return _from_c(
+            cls, c, failed_units=[decode_unit(k) for k in c.failed_keys[:n]])
+
+
+_INT, _PTR = ctypes.c_int, ctypes.c_void_p
+_GEMM = [_INT, _PTR, _PTR, _PTR, _INT, _INT, _INT]  # device, A, Bt, C, M, N, K
+_MX_GEMM = [_INT] + [_PTR] * 5 + [_INT] * 3  # device, A, SA, Bt, SB, C, M, N, K
+_UNIT_TABLE = [_INT, ctypes.POINTER(ctypes.c_uint), _INT]
+
+# Every exported function of the library: name -> (restype, argtypes).
+_BINDINGS = {
+    "cc_device_alive": (_INT, [_INT]),
+    "cc_device_count": (_INT, []),
+    "cc_device_index_for_bdf": (_INT, [_INT] * 3),
+    "cc_mfma_gemm_bf16": (_INT, _GEMM),
+    "cc_mfma_gemm_bf16_variant": (_INT, _GEMM + [_INT]),
+    "cc_mfma_gemm_fp8_variant": (_INT, _GEMM + [_INT]),
+    "cc_mfma_gemm_fp8": (_INT, _GEMM),
+    "cc_ref_gemm_f32": (_INT, _GEMM),
+    "cc_attest_device": (_INT, [_INT, _INT, ctypes.POINTER(_CReport)]),
+    "cc_report_sizeof": (_INT, []),
+    "cc_mfma_gemm_mxfp4": (_INT, _MX_GEMM),
+    "cc_ref_gemm_mxfp4_f32": (_INT, _MX_GEMM),
+    "cc_attest_mxfp4": (_INT, [_INT, _INT, ctypes.POINTER(_CMxReport)]),
+    "cc_mx_report_sizeof": (_INT, []),
+    "cc_cu_sweep": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CSweepReport)]),
+    "cc_cu_sweep_gold": (_INT, [_INT, _INT, ctypes.POINTER(ctypes.c_float)]),
+    "cc_cu_sweep_units": (_INT, _UNIT_TABLE),
+    "cc_cu_sweep_hits": (_INT, _UNIT_TABLE),
+    "cc_sweep_report_sizeof": (_INT, []),
+    "cc_attest_shutdown": (None, []),
+}
 
 
 def _load() -> ctypes.CDLL:
@@ -252,67 +260,9 @@ def _load() -> ctypes.CDLL:
             "python -m k8s_cc_manager_amd.ops.build"
         )
     lib = ctypes.CDLL(str(_LIB_PATH))
-    lib.cc_device_count.restype = ctypes.c_int
-    lib.cc_device_index_for_bdf.restype = ctypes.c_int
-    lib.cc_device_index_for_bdf.argtypes = [ctypes.c_int] * 3
-    lib.cc_attest_device.restype = ctypes.c_int
-    lib.cc_attest_device.argtypes = [
-        ctypes.c_int,
-        ctypes.c_int,
-        ctypes.POINTER(_CReport),
-    ]
-    lib.cc_mfma_gemm_bf16.restype = ctypes.c_int
-    lib.cc_mfma_gemm_bf16.argtypes = [
-        ctypes.c_int,
-        ctypes.c_void_p,
-        ctypes.c_void_p,
-        ctypes.c_void_p,
-        ctypes.c_int,
-        ctypes.c_int,
-        ctypes.c_int,
-    ]
-    lib.cc_ref_gemm_f32.restype = ctypes.c_int
-    lib.cc_ref_gemm_f32.argtypes = lib.cc_mfma_gemm_bf16.argtypes
-    lib.cc_mfma_gemm_bf16_variant.restype = ctypes.c_int
-    lib.cc_mfma_gemm_bf16_variant.argtypes = lib.cc_mfma_gemm_bf16.argtypes + [
-        ctypes.c_int
-    ]
-    lib.cc_mfma_gemm_fp8.restype = ctypes.c_int
-    lib.cc_mfma_gemm_fp8.argtypes = lib.cc_mfma_gemm_bf16.argtypes
-    lib.cc_mfma_gemm_fp8_variant.restype = ctypes.c_int
-    lib.cc_mfma_gemm_fp8_variant.argtypes = lib.cc_mfma_gemm_bf16.argtypes + [
-        ctypes.c_int
-    ]
-    lib.cc_mfma_gemm_mxfp4.restype = ctypes.c_int
-    lib.cc_mfma_gemm_mxfp4.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 5 + [
-        ctypes.c_int
-    ] * 3
-    lib.cc_ref_gemm_mxfp4_f32.restype = ctypes.c_int
-    lib.cc_ref_gemm_mxfp4_f32.argtypes = lib.cc_mfma_gemm_mxfp4.argtypes
-    lib.cc_attest_mxfp4.restype = ctypes.c_int
-    lib.cc_attest_mxfp4.argtypes = [
-        ctypes.c_int,
-        ctypes.c_int,
-        ctypes.POINTER(_CMxReport),
-    ]
-    lib.cc_mx_report_sizeof.restype = ctypes.c_int
-    lib.cc_cu_sweep.restype = ctypes.c_int
-    lib.cc_cu_sweep.argtypes = [
-        ctypes.c_int,
-        ctypes.c_int,
-        ctypes.c_int,
-        ctypes.POINTER(_CSweepReport),
-    ]
-    lib.cc_cu_sweep_gold.restype = ctypes.c_int
-    lib.cc_cu_sweep_gold.argtypes = [
-        ctypes.c_int,
-        ctypes.c_int,
-        ctypes.POINTER(ctypes.c_float),
-    ]
-    for fn in (lib.cc_cu_sweep_units, lib.cc_cu_sweep_hits):
-        fn.restype = ctypes.c_int
-        fn.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint), ctypes.c_int]
-    lib.cc_sweep_report_sizeof.restype = ctypes.c_int
+    for name, (restype, argtypes) in _BINDINGS.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -327,6 +277,18 @@ def probe_available() -> bool:
 
 def device_count() -> int:
     return _load().cc_device_count()
+
+
+def device_alive(device_index: int) -> int:
+    """Round-trip one kernel launch on the device: 0 when it answered,
+    else the library's negative status."""
+    return _load().cc_device_alive(device_index)
+
+
+def shutdown() -> None:
+    """Free everything the library caches on every device (buffers,
+    references, the last sweep's unit table)."""
+    _load().cc_attest_shutdown()
 
 
 def attest_device(device_index: int, gemm_dim: int = 1024) -> AttestReport:
@@ -641,7 +603,7 @@ def _gemm_call(fn_name: str, label: str, *args: int) -> None:
 def mfma_gemm_bf16(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
                    m: int, n: int, k: int) -> None:
     """Launch C[M,N] = A[M,K] @ Bt[N,K]^T on caller-owned device buffers
-    (torch tensors via .data_ptr()). M,N multiples of 128, K of 32."""
+    (torch tensors via .data_ptr()). M,N multiples of 128, K of 64."""
     _gemm_call("cc_mfma_gemm_bf16", "mfma_gemm_bf16",
                device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
 
@@ -655,7 +617,7 @@ def ref_gemm_f32(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
 def mfma_gemm_fp8(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
                   m: int, n: int, k: int) -> None:
     """MX-scaled fp8 e4m3 GEMM (unit scales): C = A @ Bt^T, fp32 out.
-    M,N multiples of 256, K of 256."""
+    M,N multiples of 128, K of 64."""
     _gemm_call("cc_mfma_gemm_fp8", "mfma_gemm_fp8",
                device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
 

@@ -1,0 +1,326 @@
+// Probe legs. Each takes the device context and the report and returns
+// 0, a HIP error (text in rep->error) or a negative probe status. The
+// three GEMM legs share the steps that are identical (timed_gemm,
+// cached_reference, compare_read_back); their clears and fills differ
+// and stay in the leg.
+
+// Warm launch, sync, timed launch, TF/s of the D^3 GEMM; -6 when
+// `launch` refuses the shape (returns nonzero).
+template <typename Report, typename Launch>
+static int timed_gemm(DeviceCtx& dev, Report* rep, int D, double* ms,
+                      double* tflops, Launch launch) {
+  auto checked = [&] { return launch() != 0 ? -6 : 0; };
+  CC_TRY(checked());
+  CC_CHECK(hipDeviceSynchronize());
+  CC_TRY(timed_ms(dev, rep, ms, checked));
+  *tflops = 2.0 * D * (double)D * D / (*ms * 1e-3) / 1e12;
+  return 0;
+}
+
+// The fills are deterministic per dim, so a leg's VALU reference is a
+// constant: computed (and timed) once per context — ~1.9 ms of a 2.4 ms
+// warm probe at dim 1024. *ms = 0.0 when cached.
+template <typename Report, typename Launch>
+static int cached_reference(DeviceCtx& dev, Report* rep, int* valid,
+                            double* ms, Launch launch) {
+  *ms = 0.0;
+  if (*valid) return 0;
+  CC_TRY(timed_ms(dev, rep, ms, [&] {
+    launch();
+    return 0;
+  }));
+  *valid = 1;
+  return 0;
+}
+
+// max_abs_diff of dC against dRef, the checksum of dC where the leg has
+// one, sync, read back.
+template <typename Report>
+static int compare_read_back(Report* rep, const float* dC, const float* dRef,
+                             long elems, float* dErr, float* err,
+                             unsigned long long* dSum = nullptr,
+                             unsigned long long* sum = nullptr) {
+  hipLaunchKernelGGL(max_abs_diff, dim3(1024), dim3(256), 0, 0, dC, dRef,
+                     elems, dErr);
+  if (dSum)
+    hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0, dC, elems,
+                       dSum);
+  CC_CHECK(hipDeviceSynchronize());
+  CC_CHECK(read_back(dErr, err));
+  if (dSum) CC_CHECK(read_back(dSum, sum));
+  return 0;
+}
+
+static int probe_bf16(DeviceCtx& dev, CcAttestReport* rep) {
+  MainCtx& ctx = dev.main;
+  const int D = ctx.dim;
+  const long elems = (long)D * D;
+  bf16 *dA = ctx.dA, *dB = ctx.dB;
+  float *dC = ctx.dC, *dRef = ctx.dRef, *dErr = ctx.dErr;
+  unsigned long long* dSum = ctx.dSum;
+  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
+  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
+
+  // fill (asymmetric seeds: catches row/col-swapped layouts)
+  hipLaunchKernelGGL(fill_bf16_lcg, dim3(2048), dim3(256), 0, 0, dA, elems, 1u);
+  hipLaunchKernelGGL(fill_bf16_lcg, dim3(2048), dim3(256), 0, 0, dB, elems, 7u);
+
+  // production bf16 dispatch (D is a multiple of its 128 tile)
+  CC_TRY(timed_gemm(dev, rep, D, &rep->gemm_ms, &rep->gemm_tflops,
+                    [&] { return launch_mfma_gemm(dA, dB, dC, D, D, D); }));
+  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->ref_ms, [&] {
+    dim3 rblock(16, 16), rgrid((D + 15) / 16, (D + 15) / 16);
+    hipLaunchKernelGGL(ref_gemm_f32, rgrid, rblock, 0, 0, dA, dB, dRef, D, D,
+                       D);
+  }));
+  return compare_read_back(rep, dC, dRef, elems, dErr, &rep->max_abs_err, dSum,
+                           &rep->checksum);
+}
+
+// fp8 (MX-scaled) MFMA path: same integer values, same fp32 reference,
+// bitwise requirement; the PRODUCTION fp8 dispatch
+static int probe_fp8(DeviceCtx& dev, CcAttestReport* rep) {
+  MainCtx& ctx = dev.main;
+  const int D = ctx.dim;
+  const long elems = (long)D * D;
+  float *dC = ctx.dC, *dErr = ctx.dErr;
+  hipLaunchKernelGGL(fill_fp8_lcg, dim3(2048), dim3(256), 0, 0, ctx.dA8.p,
+                     elems, 1u);
+  hipLaunchKernelGGL(fill_fp8_lcg, dim3(2048), dim3(256), 0, 0, ctx.dB8.p,
+                     elems, 7u);
+  CC_TRY(timed_gemm(dev, rep, D, &rep->fp8_ms, &rep->fp8_tflops, [&] {
+    return launch_fp8_best(ctx.dA8, ctx.dB8, dC, D, D, D);
+  }));
+  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));  // only now; no checksum
+  return compare_read_back(rep, dC, ctx.dRef, elems, dErr,
+                           &rep->fp8_max_abs_err);
+}
+
+static int probe_lds(DeviceCtx& dev, CcAttestReport* rep) {
+  uint32_t* dFail = dev.main.dFail;
+  CC_CHECK(hipMemset(dFail, 0, sizeof(uint32_t)));
+  CC_TRY(timed_ms(dev, rep, &rep->lds_ms, [&] {
+    hipLaunchKernelGGL(lds_probe, dim3(512), dim3(256), 0, 0, dFail, 8);
+    return 0;
+  }));
+  CC_CHECK(read_back(dFail, &rep->lds_failures));
+  return 0;
+}
+
+// HBM probe (dedicated dst: dRef is a cached constant)
+static int probe_hbm(DeviceCtx& dev, CcAttestReport* rep) {
+  MainCtx& ctx = dev.main;
+  long n4 = (long)ctx.dim * ctx.dim / 4;
+  CC_TRY(timed_ms(dev, rep, &rep->hbm_ms, [&] {
+    hipLaunchKernelGGL(hbm_copy_f4, dim3(4096), dim3(256), 0, 0,
+                       (const float4v*)ctx.dC.p, (float4v*)ctx.dHbm.p, n4);
+    return 0;
+  }));
+  rep->hbm_gbps = 2.0 * n4 * 16.0 / (rep->hbm_ms * 1e-3) / 1e9;
+  return 0;
+}
+
+// xGMI peer visibility + traffic. Visibility alone attests nothing
+// about link integrity: for every accessible peer, move the live result
+// buffer across the link (SDMA over xGMI) and recompute its checksum ON
+// THE PEER. Per-link bandwidth is reported (xGMI is point-to-point,
+// 7 links x ~153 GB/s per GPU — each link is individually bound).
+static int probe_xgmi(DeviceCtx& dev, CcAttestReport* rep) {
+  MainCtx& ctx = dev.main;
+  const int device = rep->device;
+  float* dC = ctx.dC;
+  unsigned long long* dSum = ctx.dSum;
+  int ndev = 0;
+  CC_CHECK(hipGetDeviceCount(&ndev));
+  rep->peer_count = ndev - 1;
+  if (ndev > kMaxDevices) ndev = kMaxDevices;
+  // Bounded per-link sample (2 MiB x 2 copies): on an 8-GPU hive the
+  // probe runs per device per transition and touches 7 links — an
+  // unbounded sample would dominate the transition step. 4 MiB per
+  // link is still real SDMA traffic with an on-peer checksum.
+  long bytes = (long)ctx.dim * ctx.dim * sizeof(float);
+  if (bytes > (2L << 20)) bytes = 2L << 20;
+  long sum_elems = bytes / sizeof(float);
+  // fresh source checksum over the sampled slice: dC now holds the
+  // fp8 result (the bf16-era rep->checksum no longer matches)
+  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
+  hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0, dC, sum_elems,
+                     dSum);
+  CC_CHECK(hipDeviceSynchronize());
+  unsigned long long src_sum = 0;
+  CC_CHECK(read_back(dSum, &src_sum));
+  // accessible peer list first; CC_ATTEST_XGMI_MAX_PEERS (0 = all)
+  // bounds how many links one probe samples — the scaling bench sets
+  // it so per-transition cost stays O(1) while the round-robin cursor
+  // still covers every link across consecutive probes
+  int acc[kMaxDevices];
+  int n_acc = 0;
+  for (int p = 0; p < ndev; ++p) {
+    if (p == device) continue;
+    int can = 0;
+    if (hipDeviceCanAccessPeer(&can, device, p) == hipSuccess && can)
+      acc[n_acc++] = p;
+  }
+  rep->peers_accessible = n_acc;
+  int max_peers = 0;
+  if (const char* mp = getenv("CC_ATTEST_XGMI_MAX_PEERS")) max_peers = atoi(mp);
+  int attempts = (max_peers > 0 && max_peers < n_acc) ? max_peers : n_acc;
+  rep->peers_attempted = attempts;
+  DeviceHop hop(device);
+  for (int t = 0; t < attempts; ++t) {
+    int p = acc[(ctx.peer_cursor + t) % (n_acc ? n_acc : 1)];
+    hipError_t pe = hipDeviceEnablePeerAccess(p, 0);
+    if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled) {
+      (void)hipGetLastError();  // clear; copy may still route via SDMA
+    }
+    // destination + checksum word live on the peer (cached there)
+    PeerCtx& pc = device_ctx(p).peer;
+    CC_CHECK(hop.to(p));
+    // grow-only: ensure() frees the smaller buffer before allocating
+    if ((long)pc.dPeerDst.bytes < bytes &&
+        pc.dPeerDst.ensure(bytes) != hipSuccess) {
+      CC_CHECK(hop.back());
+      continue;  // peer VRAM exhausted: counted accessible, not verified
+    }
+    if (pc.dPeerSum.ensure(sizeof(unsigned long long)) != hipSuccess) {
+      CC_CHECK(hop.back());
+      continue;
+    }
+    CC_CHECK(hipMemset(pc.dPeerDst, 0, bytes));
+    CC_CHECK(hop.back());
+    // timed link traffic: kPeerIters copies of the result buffer
+    const int kPeerIters = 4;
+    double ms = 0.0;
+    CC_TRY(timed_ms(dev, rep, &ms, [&] {
+      for (int it = 0; it < kPeerIters; ++it)
+        CC_CHECK(hipMemcpyPeerAsync(pc.dPeerDst, p, dC, device, bytes, 0));
+      return 0;
+    }));
+    rep->xgmi_ms += ms;
+    double gbps = (double)bytes * kPeerIters / (ms * 1e-3) / 1e9;
+    if (rep->xgmi_gbps_min == 0.0 || gbps < rep->xgmi_gbps_min)
+      rep->xgmi_gbps_min = gbps;
+    if (gbps > rep->xgmi_gbps_max) rep->xgmi_gbps_max = gbps;
+    // verify ON the peer: its own CUs must read back what crossed
+    CC_CHECK(hop.to(p));
+    CC_CHECK(hipMemset(pc.dPeerSum, 0, sizeof(unsigned long long)));
+    // checksum the SAMPLED slice only (sum_elems) — the peer buffer
+    // holds exactly `bytes`; summing all of dC would read out of bounds
+    hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0,
+                       pc.dPeerDst.p, sum_elems, pc.dPeerSum.p);
+    CC_CHECK(hipDeviceSynchronize());
+    unsigned long long peer_sum = 0;
+    CC_CHECK(read_back(pc.dPeerSum, &peer_sum));
+    CC_CHECK(hop.back());
+    if (peer_sum == src_sum) ++rep->peers_verified;
+  }
+  if (n_acc) ctx.peer_cursor = (ctx.peer_cursor + attempts) % n_acc;
+  return 0;
+}
+
+// MXFP4 leg: all 16 e2m1 codes and scale bytes {126,127,128} through
+// the fp4 decoders and the block-scale hardware, bitwise against the
+// VALU reference (exactness budget at fill_fp4_lcg).
+static int probe_mxfp4(DeviceCtx& dev, CcMxReport* rep) {
+  MxCtx& ctx = dev.mx;
+  const int D = ctx.dim;
+  const long elems = (long)D * D;
+  unsigned char *dA = ctx.dMxA, *dB = ctx.dMxB;
+  unsigned char *dSA = ctx.dMxSA, *dSB = ctx.dMxSB;
+  float *dC = ctx.dMxC, *dRef = ctx.dMxRef, *dErr = ctx.dMxErr;
+  unsigned long long* dSum = ctx.dMxSum;
+  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
+  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
+  // prefill with 0x7f7f7f7f (3.4e38, finite: max_abs_diff's fmaxf would
+  // drop a NaN): an output the kernel never wrote shows as a huge error
+  CC_CHECK(hipMemset(dC, 0x7F, elems * sizeof(float)));
+
+  hipLaunchKernelGGL(fill_fp4_lcg, dim3(2048), dim3(256), 0, 0, dA, elems / 2,
+                     1u);
+  hipLaunchKernelGGL(fill_fp4_lcg, dim3(2048), dim3(256), 0, 0, dB, elems / 2,
+                     7u);
+  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, dSA,
+                     elems / 32, 1u);
+  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, dSB,
+                     elems / 32, 7u);
+
+  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops, [&] {
+    return launch_mxfp4(dA, dSA, dB, dSB, dC, D, D, D);
+  }));
+  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms, [&] {
+    launch_ref_mxfp4(dA, dSA, dB, dSB, dRef, D, D, D);
+  }));
+  return compare_read_back(rep, dC, dRef, elems, dErr, &rep->mx_max_abs_err,
+                           dSum, &rep->mx_checksum);
+}
+
+// The golden C images for `rounds`, a constant: computed once per
+// (device, rounds). *ms = 0.0 when the cached images were used. `rep`
+// is whatever holds the error text (a report, or ErrorText).
+template <typename Report>
+static int sweep_gold(DeviceCtx& dev, Report* rep, int rounds, double* ms) {
+  SweepCtx& ctx = dev.sweep;
+  *ms = 0.0;
+  if (ctx.gold_rounds == rounds) return 0;
+  ctx.gold_rounds = 0;
+  CC_TRY(timed_ms(dev, rep, ms, [&] {
+    hipLaunchKernelGGL(cu_sweep_gold, dim3(1), dim3(1024), 0, 0,
+                       ctx.dSweepGold.p, rounds);
+    return 0;
+  }));
+  CC_CHECK(hipGetLastError());
+  ctx.gold_rounds = rounds;
+  return 0;
+}
+
+static int sweep_units_seen(const unsigned* tab) {
+  int n = 0;
+  for (int k = 0; k < CU_SWEEP_UNITS; ++k) n += tab[k * CU_SWEEP_REC] != 0;
+  return n;
+}
+
+// Sweep leg: up to 4 launches of 4 blocks per CU into one unit table,
+// until every SIMD of every CU has reported.
+static int probe_cu_sweep(DeviceCtx& dev, CcSweepReport* rep, int poison_key) {
+  SweepCtx& ctx = dev.sweep;
+  const size_t tab_b = SweepCtx::kTabWords * sizeof(unsigned);
+  unsigned* tab = ctx.hSweepTab.data();
+  CC_TRY(sweep_gold(dev, rep, rep->rounds, &rep->gold_ms));
+  ctx.valid = 0;
+  CC_CHECK(hipMemset(ctx.dSweepTab, 0, tab_b));
+  const int kMaxLaunches = 4;
+  for (int l = 0; l < kMaxLaunches; ++l) {
+    double ms = 0.0;
+    CC_TRY(timed_ms(dev, rep, &ms, [&] {
+      hipLaunchKernelGGL(cu_sweep, dim3(4 * rep->cu_count), dim3(1024), 0, 0,
+                         ctx.dSweepGold.p, ctx.dSweepTab.p, rep->rounds,
+                         poison_key);
+      return 0;
+    }));
+    CC_CHECK(hipGetLastError());
+    rep->sweep_ms += ms;
+    rep->launches = l + 1;
+    CC_CHECK(hipMemcpy(tab, ctx.dSweepTab, tab_b, hipMemcpyDeviceToHost));
+    if (sweep_units_seen(tab) >= rep->units_expected) break;
+  }
+  ctx.valid = 1;
+
+  unsigned long long xccs = 0;
+  int last_cu = -1;  // keys ascend, a CU's four SIMDs are adjacent
+  for (int k = 0; k < CU_SWEEP_UNITS; ++k) {
+    const unsigned* rec = tab + k * CU_SWEEP_REC;
+    if (!rec[0]) continue;
+    ++rep->units_seen;
+    if ((k >> 2) != last_cu) ++rep->cus_seen;
+    last_cu = k >> 2;
+    xccs |= 1ull << (k >> 10);
+    rep->mfma_failures += rec[1];
+    rep->lds_failures += rec[2];
+    if (rec[1] || rec[2]) {
+      if (rep->units_failed < 16) rep->failed_keys[rep->units_failed] = k;
+      ++rep->units_failed;
+    }
+  }
+  rep->xccs_seen = __builtin_popcountll(xccs);
+  return 0;
+}

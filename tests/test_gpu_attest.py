@@ -174,8 +174,44 @@ def test_attest_checksum_deterministic(attest):
 
 
 def test_device_alive_liveness(attest):
-    lib = attest._load()
-    assert lib.cc_device_alive(0) == 0
+    assert attest.device_count() >= 1
+    assert attest.device_alive(0) == 0
+
+
+def test_legs_keep_their_caches_across_main_dim_changes(attest):
+    """A change of the main probe's dim frees only the main probe's
+    buffers: the MXFP4 reference, the sweep's golden images and unit
+    table and the liveness word stay."""
+    mx = attest.attest_mxfp4(0, 256)
+    attest.sweep_compute_units(0, rounds=1)
+    units = attest.cu_sweep_units(0)
+    assert units
+    assert attest.device_alive(0) == 0
+    assert attest.attest_device(0, 128).ok
+    assert attest.attest_device(0, 256).ok
+    assert attest.device_alive(0) == 0
+    again = attest.attest_mxfp4(0, 256)
+    assert again.mx_ref_ms == 0.0  # cached reference
+    assert again.mx_checksum == mx.mx_checksum
+    assert attest.cu_sweep_units(0) == units
+    assert attest.sweep_compute_units(0, rounds=1).gold_ms == 0.0  # cached
+
+
+def test_shutdown_frees_every_leg(attest):
+    before = attest.attest_device(0, 128)
+    attest.attest_mxfp4(0, 256)
+    attest.sweep_compute_units(0, rounds=1)
+    assert attest.device_alive(0) == 0
+    attest.shutdown()
+    assert attest.cu_sweep_units(0) == []
+    after = attest.attest_device(0, 128)
+    assert after.ok and after.ref_ms > 0.0  # reference recomputed
+    assert after.checksum == before.checksum
+    assert attest.attest_mxfp4(0, 256).mx_ref_ms > 0.0
+    sweep = attest.sweep_compute_units(0, rounds=1)
+    assert sweep.ok and sweep.units_failed == 0 and sweep.gold_ms > 0.0
+    assert sweep.units_seen == sweep.units_expected
+    assert attest.device_alive(0) == 0
 
 
 def test_shadow_backend_transition_with_real_probe(attest):
