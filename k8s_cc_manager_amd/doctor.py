@@ -4,7 +4,8 @@ One JSON document answering the first questions an operator asks on a
 misbehaving CC node: can the host do TEE at all, is KFD alive, what do
 PCI and amdsmi each see, does the attestation library load, and (with
 ``--attest``) does a full probe pass (``--cu-sweep`` adds the
-compute-unit sweep, per XCC). Every section degrades gracefully
+compute-unit sweep, per XCC; ``--hbm-march MIB`` a verified march and
+zeroing scrub of that much VRAM). Every section degrades gracefully
 — a CPU-only box reports absence, not a stack trace.
 """
 
@@ -43,8 +44,24 @@ def _cu_sweep_section(attest, device_index: int) -> Dict[str, Any]:
     }
 
 
+def _hbm_march_section(attest, device_index: int, mib: int) -> Dict[str, Any]:
+    """The HBM march of one GPU over ``mib`` MiB of its VRAM."""
+    rep = attest.hbm_march_report(device_index, mib)
+    first = rep.first_bad_offset
+    return {
+        "device": device_index,
+        "ok": rep.ok,
+        "mib_tested": rep.bytes_tested >> 20,
+        "gbps": round(rep.gbps, 1),
+        "mismatch_words": rep.mismatch_words,
+        "first_bad_offset": None if first is None else hex(first),
+        "scrubbed": rep.scrubbed,
+        "error": rep.error,
+    }
+
+
 def collect(run_attest: bool = False, gemm_dim: int = 512,
-            cu_sweep: bool = False) -> Dict[str, Any]:
+            cu_sweep: bool = False, hbm_march_mib: int = 0) -> Dict[str, Any]:
     report: Dict[str, Any] = {"schema": "cc-doctor/v1"}
 
     # host TEE capability
@@ -136,6 +153,11 @@ def collect(run_attest: bool = False, gemm_dim: int = 512,
                     _cu_sweep_section(attest, i)
                     for i in range(att["hip_device_count"])
                 ]
+            if hbm_march_mib > 0:
+                att["hbm_march"] = [
+                    _hbm_march_section(attest, i, hbm_march_mib)
+                    for i in range(att["hip_device_count"])
+                ]
     except Exception as e:
         att["error"] = str(e)
     report["attestation"] = att
@@ -196,6 +218,11 @@ def main(argv=None) -> int:
                     help="with --attest: also run the compute-unit sweep "
                     "(every SIMD of every CU) and list CUs seen and failed "
                     "per XCC")
+    ap.add_argument("--hbm-march", type=int, default=0, metavar="MIB",
+                    help="with --attest: also march MIB MiB of every GPU's "
+                    "VRAM (verified fill, flip, scrub to zero, zero check) "
+                    "and list MiB tested, GB/s, mismatches, first bad "
+                    "offset and whether the window was left scrubbed")
     ap.add_argument(
         "--verify-attest-log",
         metavar="PATH",
@@ -215,7 +242,7 @@ def main(argv=None) -> int:
         print(json.dumps({"verified": True, "records": n}))
         return 0
     report = collect(run_attest=args.attest, gemm_dim=args.gemm_dim,
-                     cu_sweep=args.cu_sweep)
+                     cu_sweep=args.cu_sweep, hbm_march_mib=args.hbm_march)
     print(json.dumps(report, indent=2))
     return 0 if report["verdict"]["cc_capable"] or not args.attest else 1
 

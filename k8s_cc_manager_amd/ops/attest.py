@@ -220,8 +220,98 @@ class CuSweepReport:
             cls, c, failed_units=[decode_unit(k) for k in c.failed_keys[:n]])
 
 
+class _CHbmReport(ctypes.Structure):
+    _fields_ = [
+        ("device", ctypes.c_int),
+        ("chunks", ctypes.c_int),
+        ("passes", ctypes.c_int),
+        ("n_bad", ctypes.c_int),
+        ("bytes_requested", ctypes.c_longlong),
+        ("bytes_tested", ctypes.c_longlong),
+        ("chunk_bytes", ctypes.c_longlong),
+        ("origin", ctypes.c_ulonglong),
+        ("mismatch_words", ctypes.c_ulonglong),
+        ("first_bad_offset", ctypes.c_ulonglong),
+        ("bad_offset", ctypes.c_ulonglong * 16),
+        ("bad_expected", ctypes.c_uint * 16),
+        ("bad_got", ctypes.c_uint * 16),
+        ("bad_pass", ctypes.c_int * 16),
+        ("fill_ms", ctypes.c_double),
+        ("flip_ms", ctypes.c_double),
+        ("scrub_ms", ctypes.c_double),
+        ("zero_ms", ctypes.c_double),
+        ("alloc_ms", ctypes.c_double),
+        ("gbps", ctypes.c_double),
+        ("beyond_cache", ctypes.c_int),
+        ("scrubbed", ctypes.c_int),
+        ("ok", ctypes.c_int),
+        ("error", ctypes.c_char * 256),
+    ]
+
+
+# Pattern of the HBM march (ops/hbm_march.hip), keyed by the 64-bit
+# logical word index w = (origin + byte offset in window) / 4.
+HBM_MUL_LO, HBM_MUL_HI, HBM_SALT = 2654435769, 2246822519, 0x5EED0001
+_HBM_NO_OFFSET = (1 << 64) - 1
+
+
+def hbm_pattern_word(w: int, phase: int) -> int:
+    """The 32-bit word the march expects at logical word index ``w``:
+    phase 0 is ``lo*2654435769 + hi*2246822519 + 0x5EED0001`` mod 2^32
+    with lo, hi the halves of ``w``; phase 1 its complement; phase 2
+    zero."""
+    if phase == 2:
+        return 0
+    if phase not in (0, 1):
+        raise ValueError(f"phase={phase} outside 0..2")
+    p = ((w & 0xFFFFFFFF) * HBM_MUL_LO + (w >> 32) * HBM_MUL_HI
+         + HBM_SALT) & 0xFFFFFFFF
+    return p ^ 0xFFFFFFFF if phase else p
+
+
+@dataclass
+class HbmMarchReport:
+    """Result of the opt-in HBM march (``march_hbm``) or of one step on a
+    caller's buffer (``hbm_step``). Offsets are bytes from the start of
+    the window; ``bad`` holds the first 16 wrong words as (offset,
+    expected, got, pass), ``first_bad_offset`` is None when clean."""
+
+    device: int
+    bytes_requested: int
+    bytes_tested: int
+    chunk_bytes: int
+    origin: int
+    chunks: int
+    passes: int
+    mismatch_words: int
+    first_bad_offset: Optional[int]
+    bad: list
+    fill_ms: float
+    flip_ms: float
+    scrub_ms: float
+    zero_ms: float
+    alloc_ms: float
+    gbps: float
+    beyond_cache: bool
+    scrubbed: bool
+    ok: bool
+    error: str = ""
+
+    @classmethod
+    def from_c(cls, c: _CHbmReport) -> "HbmMarchReport":
+        n = max(0, min(c.n_bad, len(c.bad_offset)))
+        first = c.first_bad_offset
+        return _from_c(
+            cls, c,
+            first_bad_offset=None if first == _HBM_NO_OFFSET else first,
+            bad=[(c.bad_offset[i], c.bad_expected[i], c.bad_got[i],
+                  c.bad_pass[i]) for i in range(n)],
+            beyond_cache=bool(c.beyond_cache), scrubbed=bool(c.scrubbed))
+
+
 _INT, _PTR = ctypes.c_int, ctypes.c_void_p
-_GEMM = [_INT, _PTR, _PTR, _PTR, _INT, _INT, _INT]  # device, A, Bt, C, M, N, K
+_I64, _U64 = ctypes.c_longlong, ctypes.c_ulonglong
+_GEMM =[_INT, _PTR, _PTR, _PTR, _INT, _INT, _INT]  # device, A, Bt, C, M, N, K
 _MX_GEMM = [_INT] + [_PTR] * 5 + [_INT] * 3  # device, A, SA, Bt, SB, C, M, N, K
 _UNIT_TABLE = [_INT, ctypes.POINTER(ctypes.c_uint), _INT]
 
@@ -246,6 +336,11 @@ _BINDINGS = {
     "cc_cu_sweep_units": (_INT, _UNIT_TABLE),
     "cc_cu_sweep_hits": (_INT, _UNIT_TABLE),
     "cc_sweep_report_sizeof": (_INT, []),
+    "cc_hbm_march": (_INT, [_INT, _I64, _INT, _U64, _I64, _INT,
+                            ctypes.POINTER(_CHbmReport)]),
+    "cc_hbm_step": (_INT, [_INT, _PTR, _I64, _U64, _INT, _INT,
+                           ctypes.POINTER(_CHbmReport)]),
+    "cc_hbm_report_sizeof": (_INT, []),
     "cc_attest_shutdown": (None, []),
 }
 
@@ -455,6 +550,83 @@ def cu_sweep_hits(device_index: int) -> dict:
                     _cu_sweep_table("cc_cu_sweep_hits", device_index)))
 
 
+def hbm_step(device_index: int, ptr: int, nbytes: int, origin: int = 0,
+             check: int = -1, write: int = -1) -> HbmMarchReport:
+    """One march step on a caller-owned device buffer (a torch tensor via
+    .data_ptr()): every 16-byte vector is compared with phase ``check``
+    and then overwritten with phase ``write`` (0 pattern, 1 complement,
+    2 zero, -1 none; not both none). ``origin`` is the logical byte
+    address of the buffer's first byte, a multiple of 16. ``nbytes`` a
+    positive multiple of 16, ``ptr`` 16-aligned; anything else raises
+    with rc=-2. Mismatches are reported, not raised."""
+    c = _CHbmReport()
+    rc = _load().cc_hbm_step(device_index, ptr, nbytes, origin, check, write,
+                             ctypes.byref(c))
+    rep = HbmMarchReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"device {device_index}: hbm step runtime error: {rep.error} rc={rc}"
+        )
+    return rep
+
+
+def hbm_march_report(device_index: int, mib: int, chunk_mib: int = 1024,
+                     _origin: int = 0, _poison_offset: int = -1,
+                     _poison_after: int = 0) -> HbmMarchReport:
+    """Run the HBM march and return its report whatever it found; raises
+    only when the march itself could not run (rc != 0, e.g. rc=-2 for
+    ``mib`` < 1 or ``chunk_mib`` outside 1..1024). A window that could
+    not be allocated is a report with ``ok`` false, ``bytes_tested`` 0
+    and the amounts in ``error``."""
+    c = _CHbmReport()
+    rc = _load().cc_hbm_march(device_index, mib, chunk_mib, _origin,
+                              _poison_offset, _poison_after, ctypes.byref(c))
+    rep = HbmMarchReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"device {device_index}: hbm march runtime error: {rep.error} rc={rc}"
+        )
+    return rep
+
+
+def march_hbm(device_index: int, mib: int, chunk_mib: int = 1024,
+              _origin: int = 0, _poison_offset: int = -1,
+              _poison_after: int = 0) -> HbmMarchReport:
+    """March ``mib`` MiB of one GPU's VRAM, held as chunks of
+    ``chunk_mib``: fill with an address-keyed pattern, verify it while
+    writing its complement, verify that while writing zeros, verify the
+    zeros. The window is real VRAM taken for the duration of the call
+    and is left zeroed. Raises when a word was wrong or when the window
+    could not be allocated. ``_poison_offset`` / ``_poison_after`` flip
+    one bit between two passes (for testing the detector)."""
+    rep = hbm_march_report(device_index, mib, chunk_mib, _origin,
+                           _poison_offset, _poison_after)
+    if not rep.ok:
+        if rep.mismatch_words:
+            where = f"first at offset {rep.first_bad_offset:#x}"
+            if rep.bad:
+                _, expected, got, bad_pass = rep.bad[0]
+                where += (f" in pass {bad_pass}, expected^got="
+                          f"{expected ^ got:#010x}")
+            raise AttestationError(
+                f"device {device_index}: hbm march FAILED: "
+                f"{rep.mismatch_words} wrong word(s), {where}"
+            )
+        raise AttestationError(
+            f"device {device_index}: hbm march FAILED: {rep.error} "
+            f"({rep.passes}/4 passes)"
+        )
+    logger.info(
+        "attested device %d: hbm march %d MiB in %d chunk(s), %.0f GB/s, "
+        "scrubbed",
+        rep.device,
+        rep.bytes_tested >> 20,
+        rep.chunks,
+        rep.gbps,
+    )
+    return rep
+
+
 _GENESIS = "cc-attest-log-v1"
 
 
@@ -569,6 +741,12 @@ def attest_device_by_bdf(device) -> dict:
     sweep = None
     if os.environ.get("CC_ATTEST_CU_SWEEP", "0") == "1":
         sweep = sweep_compute_units(idx)
+    march = None
+    hbm_mib = int(os.environ.get("CC_ATTEST_HBM_MIB") or "0")
+    if hbm_mib > 0:
+        march = march_hbm(
+            idx, hbm_mib,
+            chunk_mib=int(os.environ.get("CC_ATTEST_HBM_CHUNK_MIB") or "1024"))
     summary = {
         "arch": rep.arch.split(":")[0],
         "cus": rep.cu_count,
@@ -590,6 +768,11 @@ def attest_device_by_bdf(device) -> dict:
     if sweep is not None:
         summary["cu_sweep"] = f"{sweep.units_seen}/{sweep.units_expected}"
         summary["cu_sweep_ok"] = sweep.ok
+    if march is not None:
+        summary["hbm_march_mib"] = march.bytes_tested >> 20
+        summary["hbm_march_gbps"] = round(march.gbps)
+        summary["hbm_march_ok"] = march.ok
+        summary["hbm_scrubbed"] = march.scrubbed
     return summary
 
 

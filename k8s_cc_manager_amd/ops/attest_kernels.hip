@@ -22,15 +22,18 @@
 //                      max-diff, checksum, LDS, HBM, liveness;
 //   cu_sweep.hip       compute-unit sweep: cu_sweep (per-SIMD MFMA chains
 //                      and a whole-LDS march, keyed by the hardware ID
-//                      registers) and cu_sweep_gold (its VALU reference).
+//                      registers) and cu_sweep_gold (its VALU reference);
+//   hbm_march.hip      HBM march: march_step<check, write> (address-keyed
+//                      pattern, its complement, zero; every word verified)
+//                      and march_poison.
 //
 // and the host code, included after it:
 //
-//   probe_reports.hip  the three report structs (frozen layouts);
+//   probe_reports.hip  the four report structs (frozen layouts);
 //   gemm_dispatch.hip  variant tables, launchers, production dispatch;
 //   probe_ctx.hip      CC_CHECK / CC_TRY, DevBuf, the per-leg contexts of
 //                      a DeviceCtx, timed_ms, read_back, DeviceHop;
-//   probe_legs.hip     the seven legs and the steps the GEMM legs share.
+//   probe_legs.hip     the eight legs and the steps the GEMM legs share.
 //
 // cc_attest_device runs five legs in order:
 //   1. probe_bf16  — production bf16 GEMM dispatch, timed, compared
@@ -49,9 +52,12 @@
 // cc_cu_sweep is another: cu_sweep.hip's matrix-core and whole-LDS
 // self-test on every SIMD of every CU, with the units it reached read
 // from the hardware ID registers.
+// cc_hbm_march is the third: hbm_march.hip's four verified passes over
+// an explicit window of VRAM, which is left zeroed and checked zero.
 
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -65,13 +71,14 @@
 #include "gemm_fp4.hip"
 #include "probe_kernels.hip"
 #include "cu_sweep.hip"
+#include "hbm_march.hip"
 
 #include "probe_reports.hip"
 #include "gemm_dispatch.hip"
 #include "probe_ctx.hip"
 #include "probe_legs.hip"
 
-// What the three report-returning entry points begin with: -1 for a
+// What the report-returning entry points begin with: -1 for a
 // null report; else the report zeroed and rep->device set, -5 for a
 // device outside the context table, `refuse` (a nonzero status ends the
 // call before the device is touched), hipSetDevice.
@@ -85,6 +92,19 @@ static int report_begin(Report* rep, int device,
   CC_TRY(refuse());
   CC_CHECK(hipSetDevice(device));
   return 0;
+}
+
+// What both march entry points refuse about the logical address range:
+// the kernels rely on 16-byte vectors that never straddle 2^32 words.
+static int hbm_refuse_range(CcHbmReport* rep, unsigned long long origin,
+                            unsigned long long bytes) {
+  if (origin % 16 == 0 && origin <= (1ull << 48) &&
+      bytes <= (1ull << 48) - origin)
+    return 0;
+  snprintf(rep->error, sizeof(rep->error),
+           "origin %llu not a multiple of 16, or origin + bytes above 2^48",
+           origin);
+  return -2;
 }
 
 extern "C" {
@@ -346,6 +366,116 @@ int cc_cu_sweep_hits(int device, unsigned* hits_out, int cap) {
 
 // ABI guard for CcSweepReport, as cc_report_sizeof for CcAttestReport.
 int cc_sweep_report_sizeof(void) { return (int)sizeof(struct CcSweepReport); }
+
+// The opt-in HBM march: `mib` MiB of VRAM, held as chunks of `chunk_mib`
+// (1..1024), filled, flipped, scrubbed to zero and checked zero, every
+// word verified in between (hbm_march.hip). origin: logical byte address
+// of the window's first byte (keys the pattern; 0 in production, a
+// multiple of 16). poison_offset: -1, or the window byte offset of a
+// word whose bit 0 is flipped after pass poison_after (1..3), to test
+// the detector. Anything out of range returns -2 before the device is
+// touched. rep->ok = 1 iff the whole window was allocated, all four
+// passes ran and no word was wrong; a window that could not be
+// allocated is ok = 0 with rc 0. Nothing stays allocated afterwards.
+int cc_hbm_march(int device, long long mib, int chunk_mib,
+                 unsigned long long origin, long long poison_offset,
+                 int poison_after, struct CcHbmReport* rep) {
+  hipDeviceProp_t prop;
+  CC_TRY(report_begin(rep, device, [&] {
+    rep->origin = origin;
+    rep->first_bad_offset = ~0ull;
+    auto refuse = [&](const char* what) {
+      snprintf(rep->error, sizeof(rep->error), "%s", what);
+      return -2;
+    };
+    if (mib < 1 || mib > (1ll << 28)) return refuse("mib outside 1..2^28");
+    if (chunk_mib < 1 || chunk_mib > 1024)
+      return refuse("chunk_mib outside 1..1024");
+    const long long bytes = mib << 20;
+    rep->bytes_requested = bytes;
+    rep->chunk_bytes = (long long)chunk_mib << 20;
+    CC_TRY(hbm_refuse_range(rep, origin, bytes));
+    if (poison_offset != -1) {
+      if (poison_offset < 0 || poison_offset >= bytes || poison_offset % 4)
+        return refuse("poison offset outside the window or not 4-aligned");
+      if (poison_after < 1 || poison_after > 3)
+        return refuse("poison_after outside 1..3");
+    }
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess)
+      return refuse("no such device");
+    if ((unsigned long long)bytes > prop.totalGlobalMem)
+      return refuse("window larger than the device's memory");
+    return 0;
+  }));
+
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  DeviceCtx& dev = device_ctx(device);
+  CC_CHECK(dev.events());
+  CC_CHECK(dev.hbm.acquire());
+  CC_TRY(probe_hbm_march(dev, rep, prop.multiProcessorCount, poison_offset,
+                         poison_offset == -1 ? 0 : poison_after));
+
+  rep->beyond_cache = rep->bytes_tested >= (512ll << 20);
+  rep->scrubbed = rep->passes == 4 && rep->mismatch_words == 0;
+  rep->ok = rep->bytes_tested == rep->bytes_requested && rep->scrubbed;
+  return 0;
+}
+
+// One march_step on a caller-owned device buffer (e.g. a torch tensor):
+// compare with phase `check`, overwrite with phase `write` (-1..2, -1 =
+// none, not both). bytes a positive multiple of 16, ptr 16-aligned,
+// origin as for cc_hbm_march; anything else returns -2 without
+// launching. Offsets in the report are from ptr; bad_pass stays 0. The
+// kernel time lands in fill_ms (write only), zero_ms (check only) or
+// flip_ms (both), gbps counts the bytes read plus the bytes written.
+int cc_hbm_step(int device, void* ptr, long long bytes,
+                unsigned long long origin, int check, int write,
+                struct CcHbmReport* rep) {
+  CC_TRY(report_begin(rep, device, [&] {
+    rep->origin = origin;
+    rep->first_bad_offset = ~0ull;
+    if (!ptr || (uintptr_t)ptr % 16 || bytes < 16 || bytes % 16 ||
+        check < -1 || check > 2 || write < -1 || write > 2 ||
+        (check == -1 && write == -1)) {
+      snprintf(rep->error, sizeof(rep->error),
+               "need a 16-aligned pointer, bytes a positive multiple of 16, "
+               "check and write in -1..2 and not both -1");
+      return -2;
+    }
+    return hbm_refuse_range(rep, origin, bytes);
+  }));
+  hipDeviceProp_t prop;
+  CC_CHECK(hipGetDeviceProperties(&prop, device));
+  rep->bytes_requested = bytes;
+  rep->chunk_bytes = bytes < (long long)HBM_MARCH_MAX_CHUNK
+                         ? bytes
+                         : (long long)HBM_MARCH_MAX_CHUNK;
+  rep->chunks = (int)((bytes + rep->chunk_bytes - 1) / rep->chunk_bytes);
+
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  DeviceCtx& dev = device_ctx(device);
+  CC_CHECK(dev.events());
+  CC_CHECK(dev.hbm.acquire());
+  CC_TRY(march_reset(dev, rep));
+  double* ms = check < 0 ? &rep->fill_ms
+                         : write < 0 ? &rep->zero_ms : &rep->flip_ms;
+  CC_TRY(timed_ms(dev, rep, ms, [&] {
+    launch_march(check, write, ptr, bytes, origin, 0, dev.hbm.dRes, 0,
+                 prop.multiProcessorCount);
+    return 0;
+  }));
+  CC_CHECK(hipGetLastError());
+  CC_TRY(march_collect(dev, rep));
+  rep->passes = 1;
+  rep->bytes_tested = bytes;
+  rep->gbps = ((check >= 0) + (write >= 0)) * (double)bytes / (*ms * 1e-3) / 1e9;
+  rep->beyond_cache = bytes >= (512ll << 20);
+  rep->ok = rep->mismatch_words == 0;
+  return 0;
+}
+
+// ABI guard for CcHbmReport, as cc_report_sizeof for CcAttestReport.
+int cc_hbm_report_sizeof(void) { return (int)sizeof(struct CcHbmReport); }
 
 // Free everything every device context holds (daemon shutdown / tests).
 void cc_attest_shutdown(void) {

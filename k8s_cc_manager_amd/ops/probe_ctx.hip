@@ -147,12 +147,21 @@ struct SweepCtx {
   }
 };
 
+// The HBM march (cc_hbm_march, cc_hbm_step): only the small result
+// block. The window's chunks belong to the call and are gone when it
+// returns.
+struct HbmCtx {
+  DevBuf<HbmMarchResult> dRes;
+  hipError_t acquire() { return dRes.ensure(sizeof(HbmMarchResult)); }
+};
+
 struct DeviceCtx {
   bool used = false;  // set by device_ctx(): shutdown has something to free
   MainCtx main;
   PeerCtx peer;
   MxCtx mx;
   SweepCtx sweep;
+  HbmCtx hbm;
   DevBuf<int> dLive;  // cc_device_alive's word: freed by shutdown only
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 

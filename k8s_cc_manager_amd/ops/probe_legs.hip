@@ -324,3 +324,127 @@ static int probe_cu_sweep(DeviceCtx& dev, CcSweepReport* rep, int poison_key) {
   rep->xccs_seen = __builtin_popcountll(xccs);
   return 0;
 }
+
+// The window of one march: chunks of VRAM that live for one call. A
+// DevBuf frees nothing by itself, so this does, on every path out.
+struct HbmWindow {
+  std::vector<DevBuf<u32x4>> chunks;
+  ~HbmWindow() {
+    for (auto& c : chunks) c.release();
+  }
+};
+
+// One march_step over [ptr, ptr + bytes) in launches of at most 1 GiB
+// (32-bit in-chunk indices). addr: logical byte address of ptr (origin +
+// window offset); byte0: its window offset. The grid follows the CU
+// count, 8 blocks each, fewer when the range is smaller than that.
+static void launch_march(int check, int write, void* ptr,
+                         unsigned long long bytes, unsigned long long addr,
+                         unsigned long long byte0, HbmMarchResult* res,
+                         int pass, int cu_count) {
+  for (unsigned long long at = 0; at < bytes; at += HBM_MARCH_MAX_CHUNK) {
+    const unsigned long long n = bytes - at < HBM_MARCH_MAX_CHUNK
+                                     ? bytes - at
+                                     : HBM_MARCH_MAX_CHUNK;
+    const uint32_t nvec = (uint32_t)(n / 16);
+    const uint32_t per_block = HBM_MARCH_THREADS * HBM_MARCH_UNROLL;
+    uint32_t blocks = (nvec + per_block - 1) / per_block;
+    if (blocks > 8u * cu_count) blocks = 8u * cu_count;
+    hipLaunchKernelGGL(kMarchStep[check + 1][write + 1], dim3(blocks),
+                       dim3(HBM_MARCH_THREADS), 0, 0,
+                       (u32x4*)((char*)ptr + at), nvec, (addr + at) / 4,
+                       byte0 + at, res, pass);
+  }
+}
+
+// the result block before a march: nothing counted, no first offset
+static int march_reset(DeviceCtx& dev, CcHbmReport* rep) {
+  HbmMarchResult h = {};
+  h.first_bad_offset = ~0ull;
+  CC_CHECK(hipMemcpy(dev.hbm.dRes, &h, sizeof(h), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// ... and after it, into the report
+static int march_collect(DeviceCtx& dev, CcHbmReport* rep) {
+  HbmMarchResult h;
+  CC_CHECK(hipMemcpy(&h, dev.hbm.dRes, sizeof(h), hipMemcpyDeviceToHost));
+  rep->mismatch_words = h.mismatch_words;
+  rep->first_bad_offset = h.first_bad_offset;
+  rep->n_bad = h.mismatch_words < HBM_MARCH_RECORDS ? (int)h.mismatch_words
+                                                    : HBM_MARCH_RECORDS;
+  for (int i = 0; i < rep->n_bad; ++i) {
+    rep->bad_offset[i] = h.bad_offset[i];
+    rep->bad_expected[i] = h.bad_expected[i];
+    rep->bad_got[i] = h.bad_got[i];
+    rep->bad_pass[i] = h.bad_pass[i];
+  }
+  return 0;
+}
+
+// HBM march leg: fill p, check p / write ~p, check ~p / write 0, check 0,
+// each pass over the whole window before the next starts. rep carries
+// bytes_requested, chunk_bytes and origin. poison_after: 0, or the pass
+// (1..3) after which the word at poison_offset gets bit 0 flipped. A
+// window that cannot be allocated is not a device failure: rc 0, ok 0,
+// bytes_tested 0 and the amounts in rep->error.
+static int probe_hbm_march(DeviceCtx& dev, CcHbmReport* rep, int cu_count,
+                           long long poison_offset, int poison_after) {
+  const unsigned long long bytes = rep->bytes_requested;
+  const unsigned long long chunk = rep->chunk_bytes;
+  HbmWindow win;
+  try {
+    win.chunks = std::vector<DevBuf<u32x4>>((bytes + chunk - 1) / chunk);
+  } catch (const std::bad_alloc&) {
+    CC_CHECK(hipErrorOutOfMemory);
+  }
+  rep->chunks = (int)win.chunks.size();
+  auto chunk_len = [&](size_t c) {
+    return bytes - c * chunk < chunk ? bytes - c * chunk : chunk;
+  };
+
+  const auto t0 = std::chrono::steady_clock::now();
+  unsigned long long held = 0;
+  for (size_t c = 0; c < win.chunks.size(); ++c) {
+    if (win.chunks[c].ensure(chunk_len(c)) != hipSuccess) break;
+    held += chunk_len(c);
+  }
+  rep->alloc_ms = std::chrono::duration<double, std::milli>(
+                      std::chrono::steady_clock::now() - t0)
+                      .count();
+  if (held != bytes) {
+    (void)hipGetLastError();  // the device is fine, the window was not there
+    snprintf(rep->error, sizeof(rep->error), "allocated %llu of %llu MiB",
+             held >> 20, bytes >> 20);
+    return 0;
+  }
+
+  CC_TRY(march_reset(dev, rep));
+  static const int kPhases[4][2] = {{-1, 0}, {0, 1}, {1, 2}, {2, -1}};
+  double* const ms[4] = {&rep->fill_ms, &rep->flip_ms, &rep->scrub_ms,
+                         &rep->zero_ms};
+  for (int pass = 1; pass <= 4; ++pass) {
+    CC_TRY(timed_ms(dev, rep, ms[pass - 1], [&] {
+      for (size_t c = 0; c < win.chunks.size(); ++c)
+        launch_march(kPhases[pass - 1][0], kPhases[pass - 1][1],
+                     win.chunks[c].p, chunk_len(c), rep->origin + c * chunk,
+                     c * chunk, dev.hbm.dRes, pass, cu_count);
+      return 0;
+    }));
+    CC_CHECK(hipGetLastError());
+    rep->passes = pass;
+    if (pass == poison_after) {
+      char* at = (char*)win.chunks[poison_offset / chunk].p +
+                 poison_offset % chunk;
+      hipLaunchKernelGGL(march_poison, dim3(1), dim3(64), 0, 0, (uint32_t*)at);
+      CC_CHECK(hipGetLastError());
+    }
+  }
+  CC_TRY(march_collect(dev, rep));
+  rep->bytes_tested = (long long)bytes;
+  rep->gbps = 6.0 * bytes /
+              ((rep->fill_ms + rep->flip_ms + rep->scrub_ms + rep->zero_ms) *
+               1e-3) /
+              1e9;
+  return 0;
+}

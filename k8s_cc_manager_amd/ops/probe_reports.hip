@@ -1,4 +1,4 @@
-// The three report structs of the C API. Their layouts are frozen:
+// The four report structs of the C API. Their layouts are frozen:
 // ops/attest.py mirrors each with a ctypes.Structure, and a drifted
 // mirror reads fields from wrong offsets.
 
@@ -70,11 +70,39 @@ struct CcSweepReport {
   char error[256];
 };
 
+// Report of the opt-in HBM march (cc_hbm_march) and of one step on a
+// caller's buffer (cc_hbm_step). Offsets are bytes from the start of the
+// window; a record is {offset, expected, got, pass} of one wrong word.
+struct CcHbmReport {
+  int device;
+  int chunks;                // allocations the window is held as
+  int passes;                // passes that ran over the whole window (4)
+  int n_bad;                 // records filled, <= 16
+  long long bytes_requested;
+  long long bytes_tested;    // 0 when the window could not be allocated
+  long long chunk_bytes;
+  unsigned long long origin;
+  unsigned long long mismatch_words;
+  unsigned long long first_bad_offset;  // all ones when clean
+  unsigned long long bad_offset[16];
+  unsigned int bad_expected[16];
+  unsigned int bad_got[16];
+  int bad_pass[16];          // 1..4; 0 from cc_hbm_step
+  double fill_ms, flip_ms, scrub_ms, zero_ms;  // device events, per pass
+  double alloc_ms;           // host clock around the chunk allocations
+  double gbps;               // 6 x bytes over the four pass times
+  int beyond_cache;          // bytes_tested >= 512 MiB (sizes only)
+  int scrubbed;              // pass 4 covered the window, no word ever wrong
+  int ok;
+  char error[256];
+};
+
 }  // extern "C"
 
 static_assert(sizeof(CcAttestReport) == 504, "CcAttestReport layout is frozen");
 static_assert(sizeof(CcMxReport) == 320, "CcMxReport layout is frozen");
 static_assert(sizeof(CcSweepReport) == 392, "CcSweepReport layout is frozen");
+static_assert(sizeof(CcHbmReport) == 704, "CcHbmReport layout is frozen");
 
 // Error text of a call that has no report (cc_cu_sweep_gold).
 struct ErrorText {
