@@ -12,8 +12,8 @@
 //                      _256 / _256w (256x256 8-phase deep-pipelined,
 //                      16x16x32 / 32x32x16 ops), _128u (4 blocks/CU);
 //   gemm_fp8.hip       MX-scaled OCP e4m3 MFMA GEMMs (unit e8m0 scales):
-//                      mfma_gemm_fp8_128 / _256 / _128w / _128s / _128t /
-//                      _128u / _256u / _128pc / _256x / _128sk;
+//                      mfma_gemm_fp8_128w / _128s / _128t / _128u /
+//                      _256u / _128pc / _256x;
 //   gemm_fp4.hip       MXFP4 (e2m1, real e8m0 block scales) MFMA GEMM:
 //                      mfma_gemm_mxfp4_128u;
 //   probe_kernels.hip  fills, ref_gemm_f32 (plain VALU fp32 GEMM of the
@@ -30,7 +30,7 @@
 // and the host code, included after it:
 //
 //   probe_reports.hip  the four report structs (frozen layouts);
-//   gemm_dispatch.hip  variant tables, launchers, production dispatch;
+//   gemm_dispatch.hip  named variants, launchers, production dispatch;
 //   probe_ctx.hip      CC_CHECK / CC_TRY, DevBuf, the per-leg contexts of
 //                      a DeviceCtx, timed_ms, read_back, DeviceHop;
 //   probe_legs.hip     the eight legs and the steps the GEMM legs share.
@@ -160,19 +160,20 @@ int cc_mfma_gemm_bf16(int device, const void* A, const void* Bt, void* C,
 }
 
 // Force a specific bf16 variant (perf characterization / A-B); `which`
-// indexes kBf16Variants, anything else runs variant 0.
+// is one of kBf16Forced (0-3), anything else returns -2 without launching.
 int cc_mfma_gemm_bf16_variant(int device, const void* A, const void* Bt,
                               void* C, int M, int N, int K, int which) {
-  return run_forced_variant(kBf16Variants, 4, 2, device, A, Bt, C, M, N, K,
-                            which);
+  return run_forced_variant(forced_variant(kBf16Forced, which), 2, device, A,
+                            Bt, C, M, N, K);
 }
 
 // Force a specific fp8 variant (perf characterization / A-B); `which`
-// indexes kFp8Variants (0-14), anything else runs variant 0.
+// is one of kFp8Forced (2-13), anything else returns -2 without
+// launching.
 int cc_mfma_gemm_fp8_variant(int device, const void* A, const void* Bt,
                              void* C, int M, int N, int K, int which) {
-  return run_forced_variant(kFp8Variants, 15, 1, device, A, Bt, C, M, N, K,
-                            which);
+  return run_forced_variant(forced_variant(kFp8Forced, which), 1, device, A,
+                            Bt, C, M, N, K);
 }
 
 // MX-scaled fp8 (e4m3) GEMM: C[M,N] = A[M,K] @ Bt[N,K]^T, fp8 inputs,

@@ -126,9 +126,7 @@ __device__ __forceinline__ void stage_lds(
 // them from `lane` is simplified on its own before it is inlined, the
 // shifts fold differently from the kernel's other lane arithmetic, and
 // several kernels then allocate one or two registers differently.
-// ATOMIC accumulates with the hardware fp32 atomic (split-K).
 // ---------------------------------------------------------------------------
-template <bool ATOMIC = false>
 __device__ __forceinline__ void store_acc_32x32(
     float* C, int N, int row0, int col0, const f32x16& acc, int c_rowhi,
     int c_col32) {
@@ -136,10 +134,7 @@ __device__ __forceinline__ void store_acc_32x32(
   for (int reg = 0; reg < 16; ++reg) {
     int row = row0 + (reg & 3) + 8 * (reg >> 2) + c_rowhi;
     int col = col0 + c_col32;
-    if (ATOMIC)
-      unsafeAtomicAdd(&C[(long)row * N + col], acc[reg]);
-    else
-      C[(long)row * N + col] = acc[reg];
+    C[(long)row * N + col] = acc[reg];
   }
 }
 

@@ -1,4 +1,4 @@
-// Host side of the GEMM kernels: variant tables, launchers and the
+// Host side of the GEMM kernels: the named variants, launchers and the
 // production dispatch policies. Included by attest_kernels.hip after the
 // device files.
 
@@ -25,23 +25,6 @@ static int launch_arg(dim3 grid, int threads, const void* A, const void* Bt,
   return 0;
 }
 
-// forced split-K (the tiny-grid shape at any size): slice K so the grid
-// reaches ~1024 blocks, zero C, accumulate with atomics
-static int launch_splitk(dim3 grid, int threads, const void* A, const void* Bt,
-                         void* C, int M, int N, int K, int) {
-  int nk = K / BK8;
-  long blocks = (long)grid.x * grid.y;
-  int S = (int)(1024 / (blocks ? blocks : 1));
-  if (S > nk) S = nk;
-  if (S < 2) S = 2;
-  if (hipMemsetAsync(C, 0, (long)M * N * sizeof(float), 0) != hipSuccess)
-    return -4;
-  dim3 g(grid.x, grid.y, S);
-  hipLaunchKernelGGL(mfma_gemm_fp8_128sk, g, dim3(threads), 0, 0,
-                     (const char*)A, (const char*)Bt, (float*)C, M, N, K);
-  return 0;
-}
-
 constexpr int kXcdAuto = -1;  // arg: XCD remap iff past_infinity_cache()
 
 struct GemmVariant {
@@ -49,56 +32,81 @@ struct GemmVariant {
   int k_mult;          // K must be a multiple
   int threads;
   GemmLauncher launch;
-  int arg;
+  int arg;  // what a forced run passes; production dispatch passes its own
 };
 
-// bf16 variants, indexed by `which` of cc_mfma_gemm_bf16_variant:
-// 0 = 128x128 step-3, 1 = 256x256 8-phase (16x16 op),
-// 2 = 256x256 8-phase (32x32 op), 3 = 128x128 single-buffered
-// 4-blocks/CU (measured slower than the deep pipeline — kept as the
-// recorded negative arm of the occupancy series).
-static const GemmVariant kBf16Variants[] = {
-    {BM, BN, BK, 256, launch_plain<bf16, mfma_gemm_bf16>, 0},
-    {BM2, BN2, 2 * BK2, 512, launch_arg<bf16, mfma_gemm_bf16_256>, kXcdAuto},
-    {BM2, BN2, 2 * BK2, 512, launch_arg<bf16, mfma_gemm_bf16_256w>, kXcdAuto},
-    {BM, BN, 64, 256, launch_plain<bf16, mfma_gemm_bf16_128u>, 0},
-};
-enum { kBf16_128 = 0, kBf16_256 = 1, kBf16_256w = 2 };
+// The kernels production dispatch launches, by name.
+// bf16: 128x128 step-3, 256x256 8-phase (16x16 op), 256x256 8-phase
+// (32x32 op).
+static const GemmVariant kBf16_128 = {
+    BM, BN, BK, 256, launch_plain<bf16, mfma_gemm_bf16>, 0};
+static const GemmVariant kBf16_256 = {
+    BM2, BN2, 2 * BK2, 512, launch_arg<bf16, mfma_gemm_bf16_256>, kXcdAuto};
+static const GemmVariant kBf16_256w = {
+    BM2, BN2, 2 * BK2, 512, launch_arg<bf16, mfma_gemm_bf16_256w>, kXcdAuto};
 
-// fp8 variants, indexed by `which` of cc_mfma_gemm_fp8_variant
-// (measured ladder in BASELINE.md):
-//  0 = 128-tile BK=128 double-buffered (2 blocks/CU),
-//  1 = 256-tile 8-phase deep pipeline,
+// fp8 (measured ladder in BASELINE.md): BK=64 32x32-op (4 blocks/CU;
+// production's K%64-only fall-back), BK=128 SINGLE-buffered (4
+// blocks/CU; production past 1 block/CU), producer/consumer wave split
+// (4 stage waves + 4 MFMA waves, LDS-flag handoff, no block barrier in
+// the K loop; production at <=1 block/CU).
+static const GemmVariant kFp8_128s = {
+    BM, BN, 64, 256, launch_plain<char, mfma_gemm_fp8_128s>, 0};
+static const GemmVariant kFp8_128u = {
+    BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 0};
+static const GemmVariant kFp8_128pc = {
+    BM, BN, BK8, 512, launch_arg<char, mfma_gemm_fp8_128pc>, 0};
+
+// The `which` numbers of the cc_*_variant entry points. BASELINE.md and
+// profiles/ name kernels by them, so they keep their values; a number
+// that is not listed (fp8 0, 1 and 14 were kernels that have been
+// measured out and removed) names nothing.
+struct ForcedVariant {
+  int which;
+  GemmVariant v;
+};
+
+// 3 = 128x128 single-buffered 4-blocks/CU (measured slower than the deep
+// pipeline — the recorded negative arm of the occupancy series,
+// BASELINE.md).
+static const ForcedVariant kBf16Forced[] = {
+    {0, kBf16_128},
+    {1, kBf16_256},
+    {2, kBf16_256w},
+    {3, {BM, BN, 64, 256, launch_plain<bf16, mfma_gemm_bf16_128u>, 0}},
+};
+
 //  2 = 128-tile BK=256 (1 block/CU),
-//  3 = BK=64 32x32-op (4 blocks/CU; production's K%64-only fall-back),
 //  4 = BK=128 1.5-buffered (3 blocks/CU),
-//  5 = BK=128 SINGLE-buffered (4 blocks/CU; production past 1 block/CU),
 //  6 = 256x128 tile, 512 threads (2 blocks/CU),
-//  7 = producer/consumer wave split (4 stage waves + 4 MFMA waves,
-//      LDS-flag handoff, no block barrier in the K loop; production at
-//      <=1 block/CU),
-//  8 = variant 5 + XCD remap, 9 = variant 7 + XCD remap,
+//  8 = variant 5 + XCD remap, 9 = variant 7 + XCD remap (production takes
+//      that branch only past a 256 MiB working set, so these are how a
+//      small test reaches it),
 //  10 = variant 5 + timing skew, 11 = + kt rotation, 12 = skew + rotation,
-//  13 = 256x256 @ 1 block/CU, persistent fragments, full double buffer,
-//  14 = split-K of variant 5 (hw fp32 atomics into a zeroed C).
-static const GemmVariant kFp8Variants[] = {
-    {BM, BN, BK8, 256, launch_plain<char, mfma_gemm_fp8_128>, 0},
-    {BM2, BN2, 2 * BK8, 512, launch_arg<char, mfma_gemm_fp8_256>, kXcdAuto},
-    {BM, BN, BK8L, 256, launch_plain<char, mfma_gemm_fp8_128w>, 0},
-    {BM, BN, 64, 256, launch_plain<char, mfma_gemm_fp8_128s>, 0},
-    {BM, BN, BK8, 256, launch_plain<char, mfma_gemm_fp8_128t>, 0},
-    {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 0},
-    {256, BN, BK8, 512, launch_plain<char, mfma_gemm_fp8_256u>, 0},
-    {BM, BN, BK8, 512, launch_arg<char, mfma_gemm_fp8_128pc>, 0},
-    {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 1},
-    {BM, BN, BK8, 512, launch_arg<char, mfma_gemm_fp8_128pc>, 1},
-    {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 2},
-    {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 4},
-    {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 6},
-    {256, 256, BK8, 512, launch_plain<char, mfma_gemm_fp8_256x>, 0},
-    {BM, BN, BK8, 256, launch_splitk, 0},
+//  13 = 256x256 @ 1 block/CU, persistent fragments, full double buffer.
+static const ForcedVariant kFp8Forced[] = {
+    {2, {BM, BN, BK8L, 256, launch_plain<char, mfma_gemm_fp8_128w>, 0}},
+    {3, kFp8_128s},
+    {4, {BM, BN, BK8, 256, launch_plain<char, mfma_gemm_fp8_128t>, 0}},
+    {5, kFp8_128u},
+    {6, {256, BN, BK8, 512, launch_plain<char, mfma_gemm_fp8_256u>, 0}},
+    {7, kFp8_128pc},
+    {8, {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 1}},
+    {9, {BM, BN, BK8, 512, launch_arg<char, mfma_gemm_fp8_128pc>, 1}},
+    {10, {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 2}},
+    {11, {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 4}},
+    {12, {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 6}},
+    {13, {256, 256, BK8, 512, launch_plain<char, mfma_gemm_fp8_256x>, 0}},
 };
-enum { kFp8_128s = 3, kFp8_128u = 5, kFp8_128pc = 7 };
+
+// The variant `which` names, or null.
+template <int N>
+static const GemmVariant* forced_variant(const ForcedVariant (&list)[N],
+                                         int which) {
+  for (const ForcedVariant& f : list)
+    if (f.which == which) return &f.v;
+  return nullptr;
+}
 
 // working set (both operands + fp32 C) past the 256 MiB Infinity Cache:
 // the XCD remap is enabled only then
@@ -115,7 +123,7 @@ static long variant_blocks(const GemmVariant& v, int M, int N) {
   return (long)(N / v.tile_n) * (M / v.tile_m);
 }
 
-// Launch one table entry (no sync); -2 for a shape that does not fit.
+// Launch one variant (no sync); -2 for a shape that does not fit.
 static int launch_variant(const GemmVariant& v, const void* A, const void* Bt,
                           void* C, int M, int N, int K, int arg) {
   if (!variant_fits(v, M, N, K)) return -2;
@@ -123,16 +131,16 @@ static int launch_variant(const GemmVariant& v, const void* A, const void* Bt,
   return v.launch(grid, v.threads, A, Bt, C, M, N, K, arg);
 }
 
-// Forced variant: table lookup (unknown `which` -> entry 0), launch, sync.
-static int run_forced_variant(const GemmVariant* table, int count,
-                              int elem_bytes, int device, const void* A,
-                              const void* Bt, void* C, int M, int N, int K,
-                              int which) {
+// Forced variant: launch, sync. A null `v` (a `which` that names no
+// kernel) is -2 before the device is touched.
+static int run_forced_variant(const GemmVariant* v, int elem_bytes, int device,
+                              const void* A, const void* Bt, void* C, int M,
+                              int N, int K) {
+  if (!v) return -2;
   if (hipSetDevice(device) != hipSuccess) return -3;
-  const GemmVariant& v = table[which > 0 && which < count ? which : 0];
   int arg =
-      v.arg == kXcdAuto ? past_infinity_cache(M, N, K, elem_bytes) : v.arg;
-  int rc = launch_variant(v, A, Bt, C, M, N, K, arg);
+      v->arg == kXcdAuto ? past_infinity_cache(M, N, K, elem_bytes) : v->arg;
+  int rc = launch_variant(*v, A, Bt, C, M, N, K, arg);
   if (rc != 0) return rc;
   return (int)hipDeviceSynchronize();
 }
@@ -140,8 +148,8 @@ static int run_forced_variant(const GemmVariant* table, int count,
 // Launch the best-fitting bf16 MFMA GEMM variant (no sync).
 static int launch_mfma_gemm(const void* A, const void* Bt, void* C, int M,
                             int N, int K) {
-  const GemmVariant& v128 = kBf16Variants[kBf16_128];
-  const GemmVariant& v256 = kBf16Variants[kBf16_256];
+  const GemmVariant& v128 = kBf16_128;
+  const GemmVariant& v256 = kBf16_256;
   // SMALL/MID sizes: the 128-tile step-3 kernel wins decisively below
   // ~2048² output — 407 vs 252 TF @2048³, 64 vs 51 @1024³
   // (profiles/final_kernel_sweep_r02.json): the deep 256-tile pipeline
@@ -156,8 +164,7 @@ static int launch_mfma_gemm(const void* A, const void* Bt, void* C, int M,
     // grids (935 vs 848 TF @4096^3), the 16x16x32 shape past that
     // (1129 vs 1096 @8192^3) — profiles/gemm_final_sweep_2026-09-13.json
     if (variant_blocks(v256, M, N) <= 256)
-      return launch_variant(kBf16Variants[kBf16_256w], A, Bt, C, M, N, K,
-                            swz_on);
+      return launch_variant(kBf16_256w, A, Bt, C, M, N, K, swz_on);
     return launch_variant(v256, A, Bt, C, M, N, K, swz_on);
   }
   return launch_variant(v128, A, Bt, C, M, N, K, 0);
@@ -174,14 +181,14 @@ static int launch_mfma_gemm(const void* A, const void* Bt, void* C, int M,
 // K%64-only shapes fall back to the BK=64 4-blocks/CU kernel.
 static int launch_fp8_best(const void* A, const void* Bt, void* C, int M,
                            int N, int K) {
-  const GemmVariant& pc = kFp8Variants[kFp8_128pc];
+  const GemmVariant& pc = kFp8_128pc;
   if (variant_fits(pc, M, N, K)) {
     int swz_on = past_infinity_cache(M, N, K, 1);
     if (variant_blocks(pc, M, N) <= 256)
       return launch_variant(pc, A, Bt, C, M, N, K, swz_on);
-    return launch_variant(kFp8Variants[kFp8_128u], A, Bt, C, M, N, K, swz_on);
+    return launch_variant(kFp8_128u, A, Bt, C, M, N, K, swz_on);
   }
-  return launch_variant(kFp8Variants[kFp8_128s], A, Bt, C, M, N, K, 0);
+  return launch_variant(kFp8_128s, A, Bt, C, M, N, K, 0);
 }
 
 // Launch the MXFP4 MFMA GEMM (no sync); -2 for a shape that does not

@@ -118,6 +118,22 @@ def test_mfma_gemm_bf16_variants_nonsquare_bitwise(attest, which):
         assert torch.equal(c, ref), f"which={which} trial={trial}"
 
 
+@pytest.mark.parametrize("which", [4, -1])
+def test_mfma_gemm_bf16_unknown_variant_refused(attest, which):
+    """A number that names no kernel is refused with rc=-2 and nothing
+    is launched: c stays as it was."""
+    m, n, k = 256, 256, 256
+    a = torch.ones(m, k, device="cuda").bfloat16()
+    bt = torch.ones(n, k, device="cuda").bfloat16()
+    c = torch.full((m, n), float("nan"), device="cuda", dtype=torch.float32)
+    with pytest.raises(attest.AttestationError, match="rc=-2"):
+        attest.mfma_gemm_bf16_variant(
+            0, a.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k, which
+        )
+    torch.cuda.synchronize()
+    assert torch.isnan(c).all()
+
+
 def test_mfma_gemm_256_integer_exact_race_screen(attest):
     """Integer data: any stale-LDS race shows as a bitwise mismatch."""
     m = n = 512

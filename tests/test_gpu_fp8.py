@@ -42,8 +42,7 @@ def test_fp8_deep_kernel_race_screen(attest):
     """Production dispatch at a 16-block grid (<= 1 block/CU, K%128)
     reaches the producer/consumer kernel mfma_gemm_fp8_128pc: bitwise
     integer race screen of its LDS-flag handoff across repeated runs.
-    (The 8-phase deep kernel is forced variant 1, screened in
-    test_fp8_variants_bitwise.)"""
+    (The forced variants are screened in test_fp8_variants_bitwise.)"""
     m = n = 512
     k = 768  # nk = 6: both buffers wrap three times
     a = _fp8(torch.randint(-2, 2, (m, k), device="cuda").float())
@@ -70,17 +69,19 @@ def _variant_bitwise_screen(attest, which, m, n, k):
         assert torch.equal(c, ref), f"which={which} trial={trial}"
 
 
-@pytest.mark.parametrize("which", range(15))
+FORCED = range(2, 14)
+
+
+@pytest.mark.parametrize("which", FORCED)
 def test_fp8_variants_bitwise(attest, which):
-    """Every forced fp8 variant (kFp8Variants in attest_kernels.hip: 0-7
+    """Every forced fp8 variant (kFp8Forced in gemm_dispatch.hip: 2-7
     the structure ladder, 8-12 the option arms of the p/c and 4-blk
-    kernels, 13 the 256-tile 1-blk kernel, 14 split-K) must agree
-    bitwise with the fp32 reference on integer data. Split-K's fp32
-    atomics are exact on this data in any arrival order."""
+    kernels, 13 the 256-tile 1-blk kernel) must agree bitwise with the
+    fp32 reference on integer data."""
     _variant_bitwise_screen(attest, which, 512, 512, 1024)
 
 
-@pytest.mark.parametrize("which", range(15))
+@pytest.mark.parametrize("which", FORCED)
 def test_fp8_variants_bitwise_nonsquare(attest, which):
     """The same screen at m=256, n=512, k=512: 2x4 blocks for the
     128-tile kernels and 1x2 for the 256-tile ones, so a swapped M/N in
@@ -90,7 +91,7 @@ def test_fp8_variants_bitwise_nonsquare(attest, which):
 
 def test_fp8_single_block_odd_nk_reaches_pc_kernel(attest):
     """A one-block grid with K%128 == 0 (nk = 3, odd) also goes to the
-    producer/consumer kernel, not to the step-3 kernel (variant 0)."""
+    producer/consumer kernel, not to the BK=64 fall-back."""
     m, n, k = 128, 128, 384
     a = _fp8(torch.randint(-2, 2, (m, k), device="cuda").float())
     bt = _fp8(torch.randint(-2, 2, (n, k), device="cuda").float())
@@ -99,6 +100,38 @@ def test_fp8_single_block_odd_nk_reaches_pc_kernel(attest):
     attest.mfma_gemm_fp8(0, a.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k)
     torch.cuda.synchronize()
     assert torch.equal(c, ref)
+
+
+def test_fp8_k64_only_reaches_bk64_kernel(attest):
+    """K a multiple of 64 but not of 128 (k = 192: one block, nk = 3):
+    production dispatch falls back to mfma_gemm_fp8_128s. Bitwise
+    against the torch fp32 reference on integer data."""
+    m, n, k = 128, 128, 192
+    torch.manual_seed(192)
+    a = _fp8(torch.randint(-2, 2, (m, k), device="cuda").float())
+    bt = _fp8(torch.randint(-2, 2, (n, k), device="cuda").float())
+    ref = a.float() @ bt.float().t()
+    c = torch.full((m, n), float("nan"), device="cuda", dtype=torch.float32)
+    attest.mfma_gemm_fp8(0, a.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k)
+    torch.cuda.synchronize()
+    assert torch.equal(c, ref)
+
+
+@pytest.mark.parametrize("which", [0, 14, 15, -1])
+def test_fp8_retired_variant_refused(attest, which):
+    """A number that names no kernel (0 and 14 did once, before those
+    kernels were removed) is refused with rc=-2 and nothing is launched:
+    c stays as it was."""
+    m, n, k = 256, 256, 256
+    a = _fp8(torch.ones(m, k, device="cuda"))
+    bt = _fp8(torch.ones(n, k, device="cuda"))
+    c = torch.full((m, n), float("nan"), device="cuda", dtype=torch.float32)
+    with pytest.raises(attest.AttestationError, match="rc=-2"):
+        attest.mfma_gemm_fp8_variant(
+            0, a.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k, which
+        )
+    torch.cuda.synchronize()
+    assert torch.isnan(c).all()
 
 
 @pytest.mark.parametrize("m,n,k", [(256, 512, 256), (512, 256, 1024)])
