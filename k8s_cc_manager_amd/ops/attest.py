@@ -808,15 +808,15 @@ def mfma_gemm_fp8(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
 def mfma_gemm_fp8_variant(device_index: int, a_ptr: int, bt_ptr: int,
                           c_ptr: int, m: int, n: int, k: int,
                           which: int) -> None:
-    """Force an fp8 variant: 2=128/BK256, 3=BK64 4-blk (default dispatch
-    for K%64-only shapes), 4=BK128 3-blk 1.5-buf, 5=BK128 4-blk 1-buf
-    (default dispatch past 1 block/CU), 6=256x128 tile 2-blk,
-    7=producer/consumer wave split (4 stage + 4 MFMA waves, LDS-flag
-    handoff, barrier-free K loop; default dispatch up to 1 block/CU),
-    8-12=instrumentation arms (8=5+XCD remap, 9=7+XCD remap, 10=5+skew,
-    11=5+rotation, 12=5+skew+rotation), 13=256-tile 1-blk persistent.
-    Any other number (0, 1 and 14 were kernels that have been measured
-    out and removed) raises with rc=-2 and launches nothing."""
+    """Force an fp8 variant: 3=BK64 4-blk (default dispatch for
+    K%64-only shapes), 5=BK128 4-blk 1-buf (default dispatch past 1
+    block/CU), 7=producer/consumer wave split (4 stage + 4 MFMA waves,
+    LDS-flag handoff, barrier-free K loop; default dispatch up to 1
+    block/CU), 8-12=instrumentation arms (8=5+XCD remap, 9=7+XCD remap,
+    10=5+skew, 11=5+rotation, 12=5+skew+rotation), 13=256-tile 1-blk
+    persistent. Any other number (0, 1, 2, 4, 6 and 14 were kernels that
+    have been measured out and removed) raises with rc=-2 and launches
+    nothing."""
     _gemm_call("cc_mfma_gemm_fp8_variant", f"mfma_gemm_fp8_variant({which})",
                device_index, a_ptr, bt_ptr, c_ptr, m, n, k, which)
 

@@ -12,8 +12,7 @@
 //                      _256 / _256w (256x256 8-phase deep-pipelined,
 //                      16x16x32 / 32x32x16 ops), _128u (4 blocks/CU);
 //   gemm_fp8.hip       MX-scaled OCP e4m3 MFMA GEMMs (unit e8m0 scales):
-//                      mfma_gemm_fp8_128w / _128s / _128t / _128u /
-//                      _256u / _128pc / _256x;
+//                      mfma_gemm_fp8_128s / _128u / _128pc / _256x;
 //   gemm_fp4.hip       MXFP4 (e2m1, real e8m0 block scales) MFMA GEMM:
 //                      mfma_gemm_mxfp4_128u;
 //   probe_kernels.hip  fills, ref_gemm_f32 (plain VALU fp32 GEMM of the
@@ -168,7 +167,7 @@ int cc_mfma_gemm_bf16_variant(int device, const void* A, const void* Bt,
 }
 
 // Force a specific fp8 variant (perf characterization / A-B); `which`
-// is one of kFp8Forced (2-13), anything else returns -2 without
+// is one of kFp8Forced (3, 5, 7-13), anything else returns -2 without
 // launching.
 int cc_mfma_gemm_fp8_variant(int device, const void* A, const void* Bt,
                              void* C, int M, int N, int K, int which) {

@@ -34,8 +34,6 @@ constexpr int BK = 64;   // bf16 K chunk per LDS stage (128 B rows)
 constexpr int BM2 = 256, BN2 = 256, BK2 = 64;
 constexpr int HALF_B = 16384;  // one half-tile (128 rows x 128 B)
 constexpr int BK8 = 128;       // fp8 elements per K-tile (128 B rows)
-constexpr int BK8L = 256;      // fp8 elements per K-tile (256 B rows)
-constexpr unsigned SCALE_ONE = 0x7F7F7F7Fu;  // e8m0 bias-127 = 2^0 per byte
 
 // ---------------------------------------------------------------------------
 // LDS swizzles
@@ -62,21 +60,11 @@ __device__ __forceinline__ int swz8(int byte_off) {
 }
 
 // 64-B-row image (fp8 BK=64): inject row bit 2 into bank bit 3 (byte 5
-// — whole-fragment granularity, see swz256); residual 4-way conflicts
-// on rows mod 8 accepted for the experiment.
+// — whole-fragment granularity, see docs/KERNELS.md item 5, "Swizzle
+// bits must relocate whole fragments"); residual 4-way conflicts on
+// rows mod 8 accepted for the experiment.
 __device__ __forceinline__ int swz64(int off) {
   return off ^ (((off >> 8) & 1) << 5);
-}
-
-// 256-B-row image (fp8 BK=256). Swizzle constraint learned the hard
-// way: XOR source bits must address whole fragments (>= 32 B, byte bits
-// >= 5) — a bit-4 XOR keyed on a ROW bit permutes bytes inside the
-// fragment differently for A-row m and B-row n, breaking the MFMA's
-// byte pairing (wrong results, caught by the bitwise check). Bits 5-7
-// relocate fragments wholesale and are safe; the residual is a 2-way
-// bank conflict on rows r / r+8.
-__device__ __forceinline__ int swz256(int off) {
-  return off ^ (((off >> 8) & 3) << 5) ^ (((off >> 10) & 1) << 7);
 }
 
 __device__ __forceinline__ v8i load_frag32(const char* p) {

@@ -59,8 +59,8 @@ static const GemmVariant kFp8_128pc = {
 
 // The `which` numbers of the cc_*_variant entry points. BASELINE.md and
 // profiles/ name kernels by them, so they keep their values; a number
-// that is not listed (fp8 0, 1 and 14 were kernels that have been
-// measured out and removed) names nothing.
+// that is not listed (fp8 0, 1, 2, 4, 6 and 14 were kernels that have
+// been measured out and removed) names nothing.
 struct ForcedVariant {
   int which;
   GemmVariant v;
@@ -76,20 +76,14 @@ static const ForcedVariant kBf16Forced[] = {
     {3, {BM, BN, 64, 256, launch_plain<bf16, mfma_gemm_bf16_128u>, 0}},
 };
 
-//  2 = 128-tile BK=256 (1 block/CU),
-//  4 = BK=128 1.5-buffered (3 blocks/CU),
-//  6 = 256x128 tile, 512 threads (2 blocks/CU),
 //  8 = variant 5 + XCD remap, 9 = variant 7 + XCD remap (production takes
 //      that branch only past a 256 MiB working set, so these are how a
 //      small test reaches it),
 //  10 = variant 5 + timing skew, 11 = + kt rotation, 12 = skew + rotation,
 //  13 = 256x256 @ 1 block/CU, persistent fragments, full double buffer.
 static const ForcedVariant kFp8Forced[] = {
-    {2, {BM, BN, BK8L, 256, launch_plain<char, mfma_gemm_fp8_128w>, 0}},
     {3, kFp8_128s},
-    {4, {BM, BN, BK8, 256, launch_plain<char, mfma_gemm_fp8_128t>, 0}},
     {5, kFp8_128u},
-    {6, {256, BN, BK8, 512, launch_plain<char, mfma_gemm_fp8_256u>, 0}},
     {7, kFp8_128pc},
     {8, {BM, BN, BK8, 256, launch_arg<char, mfma_gemm_fp8_128u>, 1}},
     {9, {BM, BN, BK8, 512, launch_arg<char, mfma_gemm_fp8_128pc>, 1}},

@@ -3,24 +3,27 @@
 // is the only path to the ~5 PF fp8 rate on gfx950 (non-scaled fp8 MFMA
 // runs at the bf16 rate). The kernels are the measured ladder behind
 // BASELINE.md; the numbers are the forced-variant `which` of kFp8Forced
-// in gemm_dispatch.hip (0, 1 and 14 were the 2-blocks/CU step-3 kernel,
-// the 8-phase deep pipeline and split-K: measured out and removed):
-//   mfma_gemm_fp8_128w   2   128-tile BK=256, 1 block/CU
+// in gemm_dispatch.hip:
 //   mfma_gemm_fp8_128s   3   128-tile BK=64 32x32 op, 4 blocks/CU
-//   mfma_gemm_fp8_128t   4   128-tile BK=128 1.5-buffered, 3 blocks/CU
 //   mfma_gemm_fp8_128u   5   128-tile BK=128 single-buffered, 4 blocks/CU
 //                            (8, 10, 11, 12: its option arms)
-//   mfma_gemm_fp8_256u   6   256x128 tile, 2 blocks/CU
 //   mfma_gemm_fp8_128pc  7   producer/consumer wave split (9: XCD remap)
 //   mfma_gemm_fp8_256x   13  256-tile full double buffer, 1 block/CU
+// Measured out and removed (BASELINE.md keeps the numbers):
+//   0   128-tile step-3 kernel, 2 blocks/CU
+//   1   8-phase deep pipeline
+//   2   128-tile BK=256, 1 block/CU
+//   4   128-tile BK=128 1.5-buffered, 3 blocks/CU
+//   6   256x128 tile, 2 blocks/CU
+//   14  split-K
 // Production dispatch (launch_fp8_best) launches only 128pc (K%128 == 0,
 // grid <= 256 blocks), 128u (K%128 == 0 past that) and 128s (K%64 only).
 //
 // All 128-B-row images (BK=128 fp8) use swz8 and the same 16 KiB tile /
 // half-tile staging as the bf16 kernels.
-// Fragment maps: 32x32x64 op — A row=l&31, k=(l>>5)*32+j (32 consecutive
-// fp8 = one v8i read); 16x16x128 op — A row=l&15, k=(l>>4)*32+j; Bt
-// likewise by column; C/D layout is shape-determined (same as bf16).
+// Fragment map (32x32x64 op): A row=l&31, k=(l>>5)*32+j (32 consecutive
+// fp8 = one v8i read); Bt likewise by column; C/D layout is
+// shape-determined (same as bf16).
 #pragma once
 
 #include "gemm_common.hip"
@@ -66,8 +69,9 @@ __device__ __forceinline__ void mma_64x64_fp8w(
 }
 
 // fp8 step-3 variant with BK=64 + the 32x32x64 op: 32 KiB LDS/block
-// -> 4 blocks/CU (16 waves/CU) — tests the occupancy hypothesis (the
-// BK=256 arm showed the limiter is latency hiding, not FLOP/byte).
+// -> 4 blocks/CU (16 waves/CU) — tests the occupancy hypothesis (a
+// BK=256 1-block/CU kernel, since removed, showed the limiter is latency
+// hiding, not FLOP/byte: BASELINE.md, "fp8 structure A/B").
 // Image rows are 64 B (swz64).
 __global__ __launch_bounds__(256, 4) void mfma_gemm_fp8_128s(
     const char* __restrict__ A, const char* __restrict__ Bt,
@@ -376,176 +380,4 @@ __global__ __launch_bounds__(512, 1) void mfma_gemm_fp8_256x(
       store_acc_32x32(C, N, t.block_m + t.wave_m + i * 32,
                       t.block_n + t.wave_n + j * 32, acc[i][j],
                       c_rowhi, c_col32);
-}
-
-// fp8 256x128 tile at the winner's wave occupancy: 512 threads,
-// single-buffered 48 KiB LDS (A 32 KiB + B 16 KiB) -> 2 blocks/CU =
-// 16 waves/CU, same as the 128x128 winner, but 1.33x the FLOPs per
-// staged byte (A bytes amortized over twice the output rows). Tests
-// whether the stage window is DMA-rate-bound (this wins) or
-// latency-bound (occupancy already covers it; this ties or loses to
-// the coarser 8-wave barrier).
-__global__ __launch_bounds__(512, 2) void mfma_gemm_fp8_256u(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K) {
-  __shared__ char lds[3 * 16384];  // [A: 32 KiB][B: 16 KiB]
-
-  // 8 waves: wave_m 0..192, wave_n 0/64
-  const TileCoords t =
-      tile_coords<256, BN, 1>(A, Bt, K, blockIdx.y, blockIdx.x);
-
-  f32x16 acc[2][2] = {};
-  const int lane31 = t.lane & 31;
-  const int kq_b = (t.lane >> 5) * 32;
-  const int sc_reg = mx_unit_scale();
-
-  char* As = &lds[0];
-  char* Bs = &lds[32768];
-  const int nk = K / BK8;
-  for (int kt = 0; kt < nk; ++kt) {
-    // A: 32 KiB, 4 KiB per wave; B: 16 KiB, 8 waves interleaved
-    stage_lds<swz8, 4, 7, true>(t.gA, t.row_b, (long)kt * BK8, 0, As, t.wave,
-                                t.lane);
-    stage_lds<swz8, 2, 7, false>(t.gB, t.row_b, (long)kt * BK8, 0, Bs, t.wave,
-                                 t.lane);
-    __syncthreads();
-    mma_64x64_fp8w(As, Bs, t.wave_m, t.wave_n, lane31, kq_b, acc, sc_reg);
-    __syncthreads();
-  }
-  mfma_drain();
-
-  const int c_col32 = t.lane & 31;
-  const int c_rowhi = (t.lane >> 5) * 4;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      store_acc_32x32(C, N, t.block_m + t.wave_m + i * 32,
-                      t.block_n + t.wave_n + j * 32, acc[i][j],
-                      c_rowhi, c_col32);
-}
-
-// fp8 BK=128 at 3 blocks/CU via 1.5-buffering: B double-buffered
-// (prefetch overlaps compute), A single-buffered (restaged in a serial
-// window between two barriers) -> 48 KiB LDS/block. Tests the middle
-// point of the occupancy curve (2 blocks: 1505 TF, 4 blocks: 1586).
-__global__ __launch_bounds__(256, 3) void mfma_gemm_fp8_128t(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K) {
-  __shared__ char lds[3 * 16384];  // [A][B0][B1]
-
-  const TileCoords t = tile_coords<BM, BN, 1>(A, Bt, K, blockIdx.y, blockIdx.x);
-
-  f32x4 acc[4][4] = {};
-  const int lane15 = t.lane & 15;
-  const int kq_b = (t.lane >> 4) * 32;
-
-  const int nk = K / BK8;
-  char* As = &lds[0];
-  stage_lds<swz8, 4, 7, true>(t.gA, t.row_b, 0, 0, As, t.wave, t.lane);
-  stage_lds<swz8, 4, 7, true>(t.gB, t.row_b, 0, 0, &lds[16384], t.wave, t.lane);
-  __syncthreads();
-
-  for (int kt = 0; kt < nk; ++kt) {
-    char* Bs = &lds[16384 * (1 + (kt & 1))];
-    if (kt + 1 < nk)  // B prefetch overlaps this tile's compute
-      stage_lds<swz8, 4, 7, true>(t.gB, t.row_b, (long)(kt + 1) * BK8, 0,
-                                  &lds[16384 * (1 + ((kt + 1) & 1))], t.wave,
-                                  t.lane);
-    {
-      v8i afrag[4], bfrag[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int la = (t.wave_m + i * 16 + lane15) * 128 + kq_b;
-        int lb = (t.wave_n + i * 16 + lane15) * 128 + kq_b;
-        afrag[i] = load_frag32(As + swz8(la));
-        bfrag[i] = load_frag32(Bs + swz8(lb));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0, SCALE_ONE, 0, SCALE_ONE);
-    }
-    __syncthreads();  // all reads of As done (drains B prefetch too)
-    if (kt + 1 < nk) {
-      // serial A window: restage in place, land before next compute
-      stage_lds<swz8, 4, 7, true>(t.gA, t.row_b, (long)(kt + 1) * BK8, 0, As,
-                                  t.wave, t.lane);
-      __syncthreads();
-    }
-  }
-
-  const int c_col = t.lane & 15;
-  const int c_row0 = (t.lane >> 4) * 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      store_acc_16x16(C, N, t.block_m + t.wave_m + i * 16,
-                      t.block_n + t.wave_n + j * 16, acc[i][j], c_row0, c_col);
-}
-
-// fp8 step-3 variant with BK=256: doubles FLOPs per staged byte (the
-// PMC profiles show BOTH fp8 structures park ~53% on data waits with
-// identical MFMA busy — DMA/fetch-rate-bound, so feed each 32 KiB
-// stage twice the math). 128 KiB LDS -> 1 block/CU. Image rows are
-// 256 B (swz256).
-__global__ __launch_bounds__(256, 1) void mfma_gemm_fp8_128w(
-    const char* __restrict__ A, const char* __restrict__ Bt,
-    float* __restrict__ C, int M, int N, int K) {
-  __shared__ char lds[2 * 2 * 32768];  // [buf][A|B][32 KiB]
-
-  const TileCoords t = tile_coords<BM, BN, 1>(A, Bt, K, blockIdx.y, blockIdx.x);
-
-  f32x4 acc[4][4] = {};
-  const int lane15 = t.lane & 15;
-  const int kq_b = (t.lane >> 4) * 32;
-
-  const int nk = K / BK8L;
-  stage_lds<swz256, 8, 8, true>(t.gA, t.row_b, 0, 0, &lds[0], t.wave, t.lane);
-  stage_lds<swz256, 8, 8, true>(t.gB, t.row_b, 0, 0, &lds[32768], t.wave,
-                                t.lane);
-  __syncthreads();
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    char* As = &lds[buf * 2 * 32768];
-    char* Bs = As + 32768;
-    if (kt + 1 < nk) {
-      char* An = &lds[(buf ^ 1) * 2 * 32768];
-      stage_lds<swz256, 8, 8, true>(t.gA, t.row_b, (long)(kt + 1) * BK8L, 0, An,
-                                    t.wave, t.lane);
-      stage_lds<swz256, 8, 8, true>(t.gB, t.row_b, (long)(kt + 1) * BK8L, 0,
-                                    An + 32768, t.wave, t.lane);
-    }
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      v8i afrag[4], bfrag[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int la = (t.wave_m + i * 16 + lane15) * 256 + ks * 128 + kq_b;
-        int lb = (t.wave_n + i * 16 + lane15) * 256 + ks * 128 + kq_b;
-        afrag[i] = load_frag32(As + swz256(la));
-        bfrag[i] = load_frag32(Bs + swz256(lb));
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(
-              afrag[i], bfrag[j], acc[i][j], 0, 0, 0, SCALE_ONE, 0, SCALE_ONE);
-    }
-    __syncthreads();
-  }
-
-  const int c_col = t.lane & 15;
-  const int c_row0 = (t.lane >> 4) * 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      store_acc_16x16(C, N, t.block_m + t.wave_m + i * 16,
-                      t.block_n + t.wave_n + j * 16, acc[i][j], c_row0, c_col);
 }

@@ -69,15 +69,15 @@ def _variant_bitwise_screen(attest, which, m, n, k):
         assert torch.equal(c, ref), f"which={which} trial={trial}"
 
 
-FORCED = range(2, 14)
+FORCED = [3, 5, 7, 8, 9, 10, 11, 12, 13]
 
 
 @pytest.mark.parametrize("which", FORCED)
 def test_fp8_variants_bitwise(attest, which):
-    """Every forced fp8 variant (kFp8Forced in gemm_dispatch.hip: 2-7
-    the structure ladder, 8-12 the option arms of the p/c and 4-blk
-    kernels, 13 the 256-tile 1-blk kernel) must agree bitwise with the
-    fp32 reference on integer data."""
+    """Every forced fp8 variant (kFp8Forced in gemm_dispatch.hip: 3, 5
+    and 7 the kernels production launches, 8-12 the option arms of the
+    p/c and 4-blk kernels, 13 the 256-tile 1-blk kernel) must agree
+    bitwise with the fp32 reference on integer data."""
     _variant_bitwise_screen(attest, which, 512, 512, 1024)
 
 
@@ -87,6 +87,34 @@ def test_fp8_variants_bitwise_nonsquare(attest, which):
     128-tile kernels and 1x2 for the 256-tile ones, so a swapped M/N in
     the shared epilogue or block mapping shows as a mismatch."""
     _variant_bitwise_screen(attest, which, 256, 512, 512)
+
+
+@pytest.mark.parametrize(
+    "which,m,n,k",
+    [(3, 128, 256, 64), (5, 128, 256, 128), (7, 128, 256, 128), (13, 256, 512, 128)],
+)
+def test_fp8_variants_single_k_tile(attest, which, m, n, k):
+    """nk = 1 for the kernels production can launch and the 256-tile
+    one: the K loops run only their prologue or first buffer (no
+    prefetch, no buffer wrap, no cons_done wait). Grids are 1x2 blocks,
+    so the M/N mapping is still exercised."""
+    _variant_bitwise_screen(attest, which, m, n, k)
+
+
+def test_fp8_past_one_block_per_cu_reaches_128u(attest):
+    """17 x 16 = 272 blocks (> 256) with K%128 == 0 takes production
+    dispatch to mfma_gemm_fp8_128u; the ~19 MiB working set keeps the XCD
+    remap off, as at 8192^3 short of the cache rule. nk = 2. Bitwise
+    against the torch fp32 reference on integer data."""
+    m, n, k = 2176, 2048, 256
+    torch.manual_seed(2176)
+    a = _fp8(torch.randint(-2, 2, (m, k), device="cuda").float())
+    bt = _fp8(torch.randint(-2, 2, (n, k), device="cuda").float())
+    ref = a.float() @ bt.float().t()
+    c = torch.full((m, n), float("nan"), device="cuda", dtype=torch.float32)
+    attest.mfma_gemm_fp8(0, a.data_ptr(), bt.data_ptr(), c.data_ptr(), m, n, k)
+    torch.cuda.synchronize()
+    assert torch.equal(c, ref)
 
 
 def test_fp8_single_block_odd_nk_reaches_pc_kernel(attest):
@@ -117,11 +145,11 @@ def test_fp8_k64_only_reaches_bk64_kernel(attest):
     assert torch.equal(c, ref)
 
 
-@pytest.mark.parametrize("which", [0, 14, 15, -1])
+@pytest.mark.parametrize("which", [0, 2, 4, 6, 14, 15, -1])
 def test_fp8_retired_variant_refused(attest, which):
-    """A number that names no kernel (0 and 14 did once, before those
-    kernels were removed) is refused with rc=-2 and nothing is launched:
-    c stays as it was."""
+    """A number that names no kernel (0, 2, 4, 6 and 14 did once, before
+    those kernels were removed) is refused with rc=-2 and nothing is
+    launched: c stays as it was."""
     m, n, k = 256, 256, 256
     a = _fp8(torch.ones(m, k, device="cuda"))
     bt = _fp8(torch.ones(n, k, device="cuda"))
