@@ -5,7 +5,8 @@ misbehaving CC node: can the host do TEE at all, is KFD alive, what do
 PCI and amdsmi each see, does the attestation library load, and (with
 ``--attest``) does a full probe pass (``--cu-sweep`` adds the
 compute-unit sweep, per XCC; ``--hbm-march MIB`` a verified march and
-zeroing scrub of that much VRAM). Every section degrades gracefully
+zeroing scrub of that much VRAM; ``--host-link MIB`` five verified
+passes of that much across PCIe). Every section degrades gracefully
 — a CPU-only box reports absence, not a stack trace.
 """
 
@@ -60,8 +61,34 @@ def _hbm_march_section(attest, device_index: int, mib: int) -> Dict[str, Any]:
     }
 
 
+def _host_link_section(attest, device_index: int, mib: int) -> Dict[str, Any]:
+    """The host-link leg of one GPU over ``mib`` MiB of pinned memory."""
+    rep = attest.host_link_report(device_index, mib)
+    first = rep.first_bad_offset
+    return {
+        "device": device_index,
+        "ok": rep.ok,
+        "mib_tested": rep.bytes_tested >> 20,
+        "passes": rep.passes,
+        "gbps": {
+            "pull": round(rep.pull_gbps, 1),
+            "push": round(rep.push_gbps, 1),
+            "h2d": round(rep.h2d_gbps, 1),
+            "d2h": round(rep.d2h_gbps, 1),
+            "duplex": [round(rep.duplex_pull_gbps, 1),
+                       round(rep.duplex_push_gbps, 1)],
+        },
+        "host_ms": round(rep.host_ms, 3),
+        "mismatch_words": rep.mismatch_words,
+        "first_bad_offset": None if first is None else hex(first),
+        "bad_pass": rep.bad[0][3] if rep.bad else None,
+        "error": rep.error,
+    }
+
+
 def collect(run_attest: bool = False, gemm_dim: int = 512,
-            cu_sweep: bool = False, hbm_march_mib: int = 0) -> Dict[str, Any]:
+            cu_sweep: bool = False, hbm_march_mib: int = 0,
+            host_link_mib: int = 0) -> Dict[str, Any]:
     report: Dict[str, Any] = {"schema": "cc-doctor/v1"}
 
     # host TEE capability
@@ -158,6 +185,11 @@ def collect(run_attest: bool = False, gemm_dim: int = 512,
                     _hbm_march_section(attest, i, hbm_march_mib)
                     for i in range(att["hip_device_count"])
                 ]
+            if host_link_mib > 0:
+                att["host_link"] = [
+                    _host_link_section(attest, i, host_link_mib)
+                    for i in range(att["hip_device_count"])
+                ]
     except Exception as e:
         att["error"] = str(e)
     report["attestation"] = att
@@ -223,6 +255,11 @@ def main(argv=None) -> int:
                     "VRAM (verified fill, flip, scrub to zero, zero check) "
                     "and list MiB tested, GB/s, mismatches, first bad "
                     "offset and whether the window was left scrubbed")
+    ap.add_argument("--host-link", type=int, default=0, metavar="MIB",
+                    help="with --attest: also move MIB MiB (1..1024) across "
+                    "every GPU's PCIe link in five verified passes (shader "
+                    "pull and push, copy-path h2d and d2h, duplex) and list "
+                    "GB/s per pass, mismatches and the first bad offset")
     ap.add_argument(
         "--verify-attest-log",
         metavar="PATH",
@@ -242,7 +279,8 @@ def main(argv=None) -> int:
         print(json.dumps({"verified": True, "records": n}))
         return 0
     report = collect(run_attest=args.attest, gemm_dim=args.gemm_dim,
-                     cu_sweep=args.cu_sweep, hbm_march_mib=args.hbm_march)
+                     cu_sweep=args.cu_sweep, hbm_march_mib=args.hbm_march,
+                     host_link_mib=args.host_link)
     print(json.dumps(report, indent=2))
     return 0 if report["verdict"]["cc_capable"] or not args.attest else 1
 

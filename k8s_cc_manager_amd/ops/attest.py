@@ -309,6 +309,103 @@ class HbmMarchReport:
             beyond_cache=bool(c.beyond_cache), scrubbed=bool(c.scrubbed))
 
 
+class _CHostReport(ctypes.Structure):
+    _fields_ = [
+        ("device", ctypes.c_int),
+        ("engine", ctypes.c_int),
+        ("passes", ctypes.c_int),
+        ("n_bad", ctypes.c_int),
+        ("bytes_requested", ctypes.c_longlong),
+        ("bytes_tested", ctypes.c_longlong),
+        ("origin", ctypes.c_ulonglong),
+        ("mismatch_words", ctypes.c_ulonglong),
+        ("first_bad_offset", ctypes.c_ulonglong),
+        ("bad_offset", ctypes.c_ulonglong * 16),
+        ("bad_expected", ctypes.c_uint * 16),
+        ("bad_got", ctypes.c_uint * 16),
+        ("bad_pass", ctypes.c_int * 16),
+        ("pull_ms", ctypes.c_double),
+        ("push_ms", ctypes.c_double),
+        ("h2d_ms", ctypes.c_double),
+        ("d2h_ms", ctypes.c_double),
+        ("duplex_ms", ctypes.c_double),
+        ("pull_gbps", ctypes.c_double),
+        ("push_gbps", ctypes.c_double),
+        ("h2d_gbps", ctypes.c_double),
+        ("d2h_gbps", ctypes.c_double),
+        ("duplex_pull_gbps", ctypes.c_double),
+        ("duplex_push_gbps", ctypes.c_double),
+        ("host_ms", ctypes.c_double),
+        ("alloc_ms", ctypes.c_double),
+        ("ok", ctypes.c_int),
+        ("error", ctypes.c_char * 256),
+    ]
+
+
+# The host-link leg (ops/host_link.hip) moves the march's pattern across
+# PCIe in five passes; pass k uses logical origin origin + k * 2^40.
+HOST_LINK_PASSES = ("pull", "push", "h2d", "d2h", "duplex")
+_HOST_LINK_PASS_STRIDE = 1 << 40
+
+
+def host_link_word(offset: int, pass_no: int, origin: int = 0) -> int:
+    """The 32-bit word pass ``pass_no`` (1..5) of the host-link leg
+    expects at window byte offset ``offset``: the march's pattern at
+    logical byte address ``origin + pass_no * 2^40 + offset``, phase 0 in
+    passes 1, 3 and 5 and its complement in passes 2 and 4."""
+    if not 1 <= pass_no <= len(HOST_LINK_PASSES):
+        raise ValueError(f"pass_no={pass_no} outside 1..5")
+    return hbm_pattern_word(
+        (origin + pass_no * _HOST_LINK_PASS_STRIDE + offset) // 4,
+        (pass_no + 1) & 1)
+
+
+@dataclass
+class HostLinkReport:
+    """Result of the opt-in host-link leg (``attest_host_link``), of one
+    direction on a caller's host buffer (``host_step``) or of the CPU
+    fill / compare alone (``host_pattern``). Offsets are bytes from the
+    start of the window; ``bad`` holds the first 16 wrong words as
+    (offset, expected, got, pass), ``first_bad_offset`` is None when
+    clean. ``*_ms`` are device events around the launch or copy alone,
+    ``host_ms`` is the CPU's fill and compare time."""
+
+    device: int
+    engine: int
+    bytes_requested: int
+    bytes_tested: int
+    origin: int
+    passes: int
+    mismatch_words: int
+    first_bad_offset: Optional[int]
+    bad: list
+    pull_ms: float
+    push_ms: float
+    h2d_ms: float
+    d2h_ms: float
+    duplex_ms: float
+    pull_gbps: float
+    push_gbps: float
+    h2d_gbps: float
+    d2h_gbps: float
+    duplex_pull_gbps: float
+    duplex_push_gbps: float
+    host_ms: float
+    alloc_ms: float
+    ok: bool
+    error: str = ""
+
+    @classmethod
+    def from_c(cls, c: _CHostReport) -> "HostLinkReport":
+        n = max(0, min(c.n_bad, len(c.bad_offset)))
+        first = c.first_bad_offset
+        return _from_c(
+            cls, c,
+            first_bad_offset=None if first == _HBM_NO_OFFSET else first,
+            bad=[(c.bad_offset[i], c.bad_expected[i], c.bad_got[i],
+                  c.bad_pass[i]) for i in range(n)])
+
+
 _INT, _PTR = ctypes.c_int, ctypes.c_void_p
 _I64, _U64 = ctypes.c_longlong, ctypes.c_ulonglong
 _GEMM =[_INT, _PTR, _PTR, _PTR, _INT, _INT, _INT]  # device, A, Bt, C, M, N, K
@@ -341,6 +438,13 @@ _BINDINGS = {
     "cc_hbm_step": (_INT, [_INT, _PTR, _I64, _U64, _INT, _INT,
                            ctypes.POINTER(_CHbmReport)]),
     "cc_hbm_report_sizeof": (_INT, []),
+    "cc_host_link": (_INT, [_INT, _I64, _U64, _I64, _INT,
+                            ctypes.POINTER(_CHostReport)]),
+    "cc_host_step": (_INT, [_INT, _PTR, _I64, _U64, _INT, _INT, _INT,
+                            ctypes.POINTER(_CHostReport)]),
+    "cc_host_pattern": (_INT, [_PTR, _I64, _U64, _INT, _INT,
+                               ctypes.POINTER(_CHostReport)]),
+    "cc_host_report_sizeof": (_INT, []),
     "cc_attest_shutdown": (None, []),
 }
 
@@ -627,6 +731,115 @@ def march_hbm(device_index: int, mib: int, chunk_mib: int = 1024,
     return rep
 
 
+def host_pattern(ptr: int, nbytes: int, origin: int = 0, check: int = -1,
+                 write: int = -1) -> HostLinkReport:
+    """The CPU side of the host-link leg on its own, on host memory
+    (a numpy array via .ctypes.data): fill ``nbytes`` at ``ptr`` with
+    phase ``write`` of the pattern, or compare them with phase ``check``
+    (0 pattern, 1 complement, 2 zero; exactly one of the two, the other
+    -1). Makes no GPU call. ``ptr`` 16-aligned, ``nbytes`` a positive
+    multiple of 16 of at most 1 GiB; anything else raises with rc=-2.
+    Mismatches are reported, not raised."""
+    c = _CHostReport()
+    rc = _load().cc_host_pattern(ptr, nbytes, origin, check, write,
+                                 ctypes.byref(c))
+    rep = HostLinkReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"host pattern runtime error: {rep.error} rc={rc}")
+    return rep
+
+
+def host_step(device_index: int, ptr: int, nbytes: int, origin: int = 0,
+              check: int = -1, write: int = -1,
+              engine: int = 0) -> HostLinkReport:
+    """One direction of the host link on caller-owned host memory (a
+    numpy array via .ctypes.data). ``check`` (phase 0..2) sends the
+    buffer host -> device and compares it there; ``write`` generates the
+    pattern on the device and lands it in the buffer; exactly one of the
+    two, the other -1. ``engine`` 0 is the shader on the mapped range
+    (link_pull / link_push), 1 the runtime's copy path with a device
+    staging buffer. The range is page-locked for the call unless it
+    already is. ``ptr`` 16-aligned, ``nbytes`` a positive multiple of 16
+    of at most 1 GiB; anything else raises with rc=-2. Mismatches are
+    reported, not raised."""
+    c = _CHostReport()
+    rc = _load().cc_host_step(device_index, ptr, nbytes, origin, check, write,
+                              engine, ctypes.byref(c))
+    rep = HostLinkReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"device {device_index}: host step runtime error: {rep.error} rc={rc}"
+        )
+    return rep
+
+
+def host_link_report(device_index: int, mib: int, _origin: int = 0,
+                     _poison_offset: int = -1,
+                     _poison_pass: int = 0) -> HostLinkReport:
+    """Run the host-link leg and return its report whatever it found;
+    raises only when the leg itself could not run (rc != 0, e.g. rc=-2
+    for ``mib`` outside 1..1024). Buffers that could not be allocated
+    are a report with ``ok`` false, ``bytes_tested`` 0 and the amounts in
+    ``error``."""
+    c = _CHostReport()
+    rc = _load().cc_host_link(device_index, mib, _origin, _poison_offset,
+                              _poison_pass, ctypes.byref(c))
+    rep = HostLinkReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"device {device_index}: host link runtime error: {rep.error} rc={rc}"
+        )
+    return rep
+
+
+def attest_host_link(device_index: int, mib: int, _origin: int = 0,
+                     _poison_offset: int = -1,
+                     _poison_pass: int = 0) -> HostLinkReport:
+    """Move ``mib`` MiB across the PCIe link of one GPU five times, every
+    word checked on the far side: the shader loads a CPU-filled pinned
+    window (pull) and stores into it (push), the runtime's copy path
+    carries it to the device (h2d) and back (d2h), and one launch does
+    both directions at once (duplex). The pinned window and the device
+    buffer live for the call. Raises when a word was wrong, when a pass
+    did not run or when the buffers could not be allocated; there is no
+    bandwidth floor here. ``_poison_offset`` / ``_poison_pass`` make the
+    CPU flip one bit between a pass's write and its check (for testing
+    the detector)."""
+    rep = host_link_report(device_index, mib, _origin, _poison_offset,
+                           _poison_pass)
+    if not rep.ok:
+        if rep.mismatch_words:
+            where = f"first at offset {rep.first_bad_offset:#x}"
+            if rep.bad:
+                _, expected, got, bad_pass = rep.bad[0]
+                name = (HOST_LINK_PASSES[bad_pass - 1]
+                        if 1 <= bad_pass <= len(HOST_LINK_PASSES) else "?")
+                where += (f" in pass {bad_pass} ({name}), expected^got="
+                          f"{expected ^ got:#010x}")
+            raise AttestationError(
+                f"device {device_index}: host link FAILED: "
+                f"{rep.mismatch_words} wrong word(s), {where}"
+            )
+        raise AttestationError(
+            f"device {device_index}: host link FAILED: {rep.error} "
+            f"({rep.passes}/5 passes)"
+        )
+    logger.info(
+        "attested device %d: host link %d MiB, pull %.1f push %.1f h2d %.1f "
+        "d2h %.1f GB/s, duplex %.1f + %.1f GB/s",
+        rep.device,
+        rep.bytes_tested >> 20,
+        rep.pull_gbps,
+        rep.push_gbps,
+        rep.h2d_gbps,
+        rep.d2h_gbps,
+        rep.duplex_pull_gbps,
+        rep.duplex_push_gbps,
+    )
+    return rep
+
+
 _GENESIS = "cc-attest-log-v1"
 
 
@@ -747,6 +960,18 @@ def attest_device_by_bdf(device) -> dict:
         march = march_hbm(
             idx, hbm_mib,
             chunk_mib=int(os.environ.get("CC_ATTEST_HBM_CHUNK_MIB") or "1024"))
+    link = None
+    host_mib = int(os.environ.get("CC_ATTEST_HOST_MIB") or "0")
+    if host_mib > 0:
+        link = attest_host_link(idx, host_mib)
+        # an operator's own floor for the copy path; the project ships none
+        floor = float(os.environ.get("CC_ATTEST_HOST_MIN_GBPS") or "0")
+        if floor > 0 and min(link.h2d_gbps, link.d2h_gbps) < floor:
+            raise AttestationError(
+                f"device {idx}: host link below CC_ATTEST_HOST_MIN_GBPS="
+                f"{floor:g}: h2d {link.h2d_gbps:.1f} GB/s, "
+                f"d2h {link.d2h_gbps:.1f} GB/s"
+            )
     summary = {
         "arch": rep.arch.split(":")[0],
         "cus": rep.cu_count,
@@ -773,6 +998,13 @@ def attest_device_by_bdf(device) -> dict:
         summary["hbm_march_gbps"] = round(march.gbps)
         summary["hbm_march_ok"] = march.ok
         summary["hbm_scrubbed"] = march.scrubbed
+    if link is not None:
+        summary["host_link_mib"] = link.bytes_tested >> 20
+        summary["host_link_gbps"] = [
+            round(link.pull_gbps), round(link.push_gbps),
+            round(link.h2d_gbps), round(link.d2h_gbps)
+        ]
+        summary["host_link_ok"] = link.ok
     return summary
 
 

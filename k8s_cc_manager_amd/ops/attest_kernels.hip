@@ -24,15 +24,20 @@
 //                      registers) and cu_sweep_gold (its VALU reference);
 //   hbm_march.hip      HBM march: march_step<check, write> (address-keyed
 //                      pattern, its complement, zero; every word verified)
-//                      and march_poison.
+//                      and march_poison;
+//   host_link.hip      host link: link_pull / link_push / link_duplex, the
+//                      same pattern loaded and stored by the shader across
+//                      PCIe on mapped, page-locked host memory.
 //
 // and the host code, included after it:
 //
-//   probe_reports.hip  the four report structs (frozen layouts);
+//   probe_reports.hip  the five report structs (frozen layouts);
 //   gemm_dispatch.hip  named variants, launchers, production dispatch;
 //   probe_ctx.hip      CC_CHECK / CC_TRY, DevBuf, the per-leg contexts of
 //                      a DeviceCtx, timed_ms, read_back, DeviceHop;
-//   probe_legs.hip     the eight legs and the steps the GEMM legs share.
+//   host_pattern.hip   the CPU fill and compare of the host-link leg
+//                      (plain C++, no HIP call);
+//   probe_legs.hip     the ten legs and the steps the GEMM legs share.
 //
 // cc_attest_device runs five legs in order:
 //   1. probe_bf16  — production bf16 GEMM dispatch, timed, compared
@@ -53,6 +58,10 @@
 // from the hardware ID registers.
 // cc_hbm_march is the third: hbm_march.hip's four verified passes over
 // an explicit window of VRAM, which is left zeroed and checked zero.
+// cc_host_link is the fourth: five verified passes of that pattern across
+// PCIe, both engines (shader and the runtime's copy path), both
+// directions and both at once, on a pinned host window that lives for
+// the call.
 
 #include <hip/hip_runtime.h>
 
@@ -71,10 +80,12 @@
 #include "probe_kernels.hip"
 #include "cu_sweep.hip"
 #include "hbm_march.hip"
+#include "host_link.hip"
 
 #include "probe_reports.hip"
 #include "gemm_dispatch.hip"
 #include "probe_ctx.hip"
+#include "host_pattern.hip"
 #include "probe_legs.hip"
 
 // What the report-returning entry points begin with: -1 for a
@@ -93,9 +104,11 @@ static int report_begin(Report* rep, int device,
   return 0;
 }
 
-// What both march entry points refuse about the logical address range:
-// the kernels rely on 16-byte vectors that never straddle 2^32 words.
-static int hbm_refuse_range(CcHbmReport* rep, unsigned long long origin,
+// What the march and host-link entry points refuse about the logical
+// address range: the kernels rely on 16-byte vectors that never straddle
+// 2^32 words.
+template <typename Report>
+static int hbm_refuse_range(Report* rep, unsigned long long origin,
                             unsigned long long bytes) {
   if (origin % 16 == 0 && origin <= (1ull << 48) &&
       bytes <= (1ull << 48) - origin)
@@ -476,6 +489,176 @@ int cc_hbm_step(int device, void* ptr, long long bytes,
 
 // ABI guard for CcHbmReport, as cc_report_sizeof for CcAttestReport.
 int cc_hbm_report_sizeof(void) { return (int)sizeof(struct CcHbmReport); }
+
+// What cc_host_step and cc_host_pattern refuse about a caller's host
+// range and direction, with the text in rep->error.
+static int host_refuse_range(CcHostReport* rep, const void* host_ptr,
+                             long long nbytes, unsigned long long origin,
+                             int check, int write) {
+  const bool one_way = (check >= 0 && check <= 2 && write == -1) ||
+                       (write >= 0 && write <= 2 && check == -1);
+  if (!host_ptr || (uintptr_t)host_ptr % 16 || nbytes < 16 || nbytes % 16 ||
+      nbytes > (long long)HOST_LINK_MAX_BYTES || !one_way) {
+    snprintf(rep->error, sizeof(rep->error),
+             "need a 16-aligned pointer, nbytes a positive multiple of 16 of "
+             "at most 1 GiB, and exactly one of check / write in 0..2 with "
+             "the other -1");
+    return -2;
+  }
+  return hbm_refuse_range(rep, origin, nbytes);
+}
+
+// The opt-in host-link leg: `mib` MiB (1..1024) of page-locked host
+// memory H and as much device memory D, both allocated for the call.
+// Five passes move the march's pattern across PCIe and check every word
+// on the far side (probe_host_link): pull and push by the shader on the
+// mapped window, h2d and d2h by the runtime's copy path, and a duplex
+// launch that does both at once. Pass k (1..5) uses logical origin
+// origin + k * 2^40; origin is a multiple of 16 with origin + 6 * 2^40
+// at most 2^48. poison_offset: -1, or the window byte offset of a word
+// of H whose bit 0 the CPU flips in pass poison_pass (1..5) between that
+// pass's write and its check, to test the detector. Anything out of
+// range returns -2 before anything is allocated or launched. rep->ok = 1
+// iff all five passes ran, no word was wrong and every rate is above
+// zero; there is no bandwidth floor. Buffers that could not be allocated
+// are ok = 0 with rc 0. Nothing stays allocated or pinned afterwards.
+int cc_host_link(int device, long long mib, unsigned long long origin,
+                 long long poison_offset, int poison_pass,
+                 struct CcHostReport* rep) {
+  CC_TRY(report_begin(rep, device, [&] {
+    rep->origin = origin;
+    rep->first_bad_offset = ~0ull;
+    auto refuse = [&](const char* what) {
+      snprintf(rep->error, sizeof(rep->error), "%s", what);
+      return -2;
+    };
+    if (mib < 1 || mib > 1024) return refuse("mib outside 1..1024");
+    rep->bytes_requested = mib << 20;
+    CC_TRY(hbm_refuse_range(rep, origin, 6 * HOST_LINK_PASS_STRIDE));
+    if (poison_offset != -1) {
+      if (poison_offset < 0 || poison_offset >= rep->bytes_requested ||
+          poison_offset % 4)
+        return refuse("poison offset outside the window or not 4-aligned");
+      if (poison_pass < 1 || poison_pass > 5)
+        return refuse("poison_pass outside 1..5");
+    }
+    return 0;
+  }));
+  hipDeviceProp_t prop;
+  CC_CHECK(hipGetDeviceProperties(&prop, device));
+
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  DeviceCtx& dev = device_ctx(device);
+  CC_CHECK(dev.events());
+  CC_CHECK(dev.host.acquire());
+  CC_TRY(probe_host_link(dev, rep, prop.multiProcessorCount, poison_offset,
+                         poison_offset == -1 ? 0 : poison_pass));
+
+  rep->ok = rep->passes == 5 && rep->mismatch_words == 0 &&
+            rep->pull_gbps > 0.0 && rep->push_gbps > 0.0 &&
+            rep->h2d_gbps > 0.0 && rep->d2h_gbps > 0.0 &&
+            rep->duplex_pull_gbps > 0.0 && rep->duplex_push_gbps > 0.0;
+  return 0;
+}
+
+// One direction of the host link on caller-owned host memory (e.g. a
+// numpy array), the counterpart of cc_hbm_step. Exactly one of check /
+// write is a phase 0..2, the other -1. check: the data flows host ->
+// device and is compared on the device, by link_pull on the mapped range
+// (engine 0) or by a copy into a staging buffer and march_step there
+// (engine 1). write: the pattern is generated on the device and lands in
+// the caller's memory, by link_push (engine 0) or by a march_step fill
+// of the staging buffer and a copy (engine 1). The range is page-locked
+// for the call with hipHostRegister unless it already is, and
+// unregistered on every path out; device and managed memory are refused.
+// host_ptr 16-aligned, nbytes a positive multiple of 16 of at most
+// 1 GiB, origin as for cc_hbm_step; anything else returns -2 before the
+// device is touched. Bytes outside the range are never written. Offsets
+// in the report are from host_ptr; bad_pass stays 0. The time lands in
+// pull_ms / push_ms (engine 0) or h2d_ms / d2h_ms (engine 1, the copy
+// alone).
+int cc_host_step(int device, void* host_ptr, long long nbytes,
+                 unsigned long long origin, int check, int write, int engine,
+                 struct CcHostReport* rep) {
+  CC_TRY(report_begin(rep, device, [&] {
+    rep->origin = origin;
+    rep->engine = engine;
+    rep->first_bad_offset = ~0ull;
+    if (engine != 0 && engine != 1) {
+      snprintf(rep->error, sizeof(rep->error), "engine %d outside 0..1",
+               engine);
+      return -2;
+    }
+    return host_refuse_range(rep, host_ptr, nbytes, origin, check, write);
+  }));
+  rep->bytes_requested = nbytes;
+  hipDeviceProp_t prop;
+  CC_CHECK(hipGetDeviceProperties(&prop, device));
+
+  // already page-locked (hipHostMalloc or the caller's registration)?
+  hipPointerAttribute_t attr = {};
+  bool pinned = false;
+  if (hipPointerGetAttributes(&attr, host_ptr) != hipSuccess) {
+    (void)hipGetLastError();  // ordinary memory the runtime has not seen
+  } else if (attr.type == hipMemoryTypeHost) {
+    pinned = true;
+  } else if (attr.type != hipMemoryTypeUnregistered) {
+    snprintf(rep->error, sizeof(rep->error),
+             "host_ptr is device or managed memory (type %d)", (int)attr.type);
+    return -2;
+  }
+
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  DeviceCtx& dev = device_ctx(device);
+  CC_CHECK(dev.events());
+  CC_CHECK(dev.host.acquire());
+  HostWindow win;
+  if (!pinned) {
+    CC_CHECK(hipHostRegister(host_ptr, nbytes, hipHostRegisterMapped));
+    win.registered = host_ptr;
+  }
+  void* dptr = nullptr;
+  CC_CHECK(hipHostGetDevicePointer(&dptr, host_ptr, 0));
+  CC_TRY(probe_host_step(dev, rep, win, host_ptr, dptr, check, write,
+                         prop.multiProcessorCount));
+  rep->ok = rep->passes == 1 && rep->mismatch_words == 0;
+  return 0;
+}
+
+// The CPU fill (write) or compare (check) of the host-link leg on its
+// own, on any host memory: no HIP call, so it runs without a GPU.
+// Arguments and refusals as cc_host_step's; rep->device is -1 and the
+// time lands in host_ms.
+int cc_host_pattern(void* host_ptr, long long nbytes,
+                    unsigned long long origin, int check, int write,
+                    struct CcHostReport* rep) {
+  if (!rep) return -1;
+  __builtin_memset(rep, 0, sizeof(*rep));
+  rep->device = -1;
+  rep->origin = origin;
+  rep->first_bad_offset = ~0ull;
+  CC_TRY(host_refuse_range(rep, host_ptr, nbytes, origin, check, write));
+  rep->bytes_requested = nbytes;
+  HbmMarchResult res = {};
+  res.first_bad_offset = ~0ull;
+  const auto t0 = std::chrono::steady_clock::now();
+  if (write >= 0)
+    host_pattern_fill((uint32_t*)host_ptr, nbytes / 4, origin / 4, write);
+  else
+    host_pattern_compare((const uint32_t*)host_ptr, nbytes / 4, origin / 4, 0,
+                         check, 0, &res);
+  rep->host_ms = std::chrono::duration<double, std::milli>(
+                     std::chrono::steady_clock::now() - t0)
+                     .count();
+  link_report(res, rep);
+  rep->passes = 1;
+  rep->bytes_tested = nbytes;
+  rep->ok = rep->mismatch_words == 0;
+  return 0;
+}
+
+// ABI guard for CcHostReport, as cc_report_sizeof for CcAttestReport.
+int cc_host_report_sizeof(void) { return (int)sizeof(struct CcHostReport); }
 
 // Free everything every device context holds (daemon shutdown / tests).
 void cc_attest_shutdown(void) {

@@ -155,6 +155,14 @@ struct HbmCtx {
   hipError_t acquire() { return dRes.ensure(sizeof(HbmMarchResult)); }
 };
 
+// The host-link leg (cc_host_link, cc_host_step): only the device result
+// block. The pinned window, a registration and the staging buffer belong
+// to the call.
+struct HostCtx {
+  DevBuf<HbmMarchResult> dRes;
+  hipError_t acquire() { return dRes.ensure(sizeof(HbmMarchResult)); }
+};
+
 struct DeviceCtx {
   bool used = false;  // set by device_ctx(): shutdown has something to free
   MainCtx main;
@@ -162,6 +170,7 @@ struct DeviceCtx {
   MxCtx mx;
   SweepCtx sweep;
   HbmCtx hbm;
+  HostCtx host;
   DevBuf<int> dLive;  // cc_device_alive's word: freed by shutdown only
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 

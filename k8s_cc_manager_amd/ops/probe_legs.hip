@@ -448,3 +448,266 @@ static int probe_hbm_march(DeviceCtx& dev, CcHbmReport* rep, int cu_count,
               1e9;
   return 0;
 }
+
+// The buffers of one host-link call: a pinned, mapped host window, a
+// device staging buffer, and a registration of caller-owned memory. All
+// are released on every path out.
+struct HostWindow {
+  void* host = nullptr;        // hipHostMalloc
+  void* registered = nullptr;  // hipHostRegister of the caller's range
+  DevBuf<u32x4> staging;
+  ~HostWindow() {
+    if (host) (void)hipHostFree(host);
+    if (registered) (void)hipHostUnregister(registered);
+    staging.release();
+  }
+};
+
+// link_pull (check >= 0) or link_push (write >= 0) over [dptr, dptr +
+// bytes), bytes <= 1 GiB; arguments as launch_march's.
+static void launch_link(int check, int write, void* dptr,
+                        unsigned long long bytes, unsigned long long addr,
+                        unsigned long long byte0, HbmMarchResult* res,
+                        int pass) {
+  const uint32_t nvec = (uint32_t)(bytes / 16);
+  hipLaunchKernelGGL(check >= 0 ? kLinkPull[check] : kLinkPush[write],
+                     dim3(host_link_blocks(nvec)),
+                     dim3(HOST_LINK_THREADS), 0, 0, (u32x4*)dptr, nvec,
+                     addr / 4, byte0, res, pass);
+}
+
+// the device result block before a host-link call
+static int link_reset(DeviceCtx& dev, CcHostReport* rep) {
+  HbmMarchResult h = {};
+  h.first_bad_offset = ~0ull;
+  CC_CHECK(hipMemcpy(dev.host.dRes, &h, sizeof(h), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// a result block into the report
+static void link_report(const HbmMarchResult& h, CcHostReport* rep) {
+  rep->mismatch_words = h.mismatch_words;
+  rep->first_bad_offset = h.first_bad_offset;
+  rep->n_bad = h.mismatch_words < HBM_MARCH_RECORDS ? (int)h.mismatch_words
+                                                    : HBM_MARCH_RECORDS;
+  for (int i = 0; i < rep->n_bad; ++i) {
+    rep->bad_offset[i] = h.bad_offset[i];
+    rep->bad_expected[i] = h.bad_expected[i];
+    rep->bad_got[i] = h.bad_got[i];
+    rep->bad_pass[i] = h.bad_pass[i];
+  }
+}
+
+// ... and after it: what the kernels found, then what the CPU found
+static int link_collect(DeviceCtx& dev, CcHostReport* rep,
+                        const HbmMarchResult& cpu) {
+  HbmMarchResult h;
+  CC_CHECK(hipMemcpy(&h, dev.host.dRes, sizeof(h), hipMemcpyDeviceToHost));
+  host_pattern_merge(&h, cpu);
+  link_report(h, rep);
+  return 0;
+}
+
+static double link_gbps(unsigned long long bytes, double ms) {
+  return ms > 0.0 ? (double)bytes / (ms * 1e-3) / 1e9 : 0.0;
+}
+
+// Host-link leg: five verified passes over a pinned host window H and a
+// device buffer D of the same size (pull, push, h2d, d2h, duplex), pass k
+// at logical origin origin + k * 2^40, odd passes in phase 0 and even
+// ones in phase 1. Every pass runs even after a mismatch. The CPU
+// touches H only before a launch or after its synchronise (timed_ms
+// ends in one). poison_pass: 0, or the pass (1..5) in which the CPU flips
+// bit 0 of the word at poison_offset between that pass's write and its
+// check. Buffers that cannot be allocated are not a device failure: rc
+// 0, ok 0, bytes_tested 0 and the amounts in rep->error.
+static int probe_host_link(DeviceCtx& dev, CcHostReport* rep, int cu_count,
+                           long long poison_offset, int poison_pass) {
+  using clock = std::chrono::steady_clock;
+  auto ms_since = [](clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(clock::now() - t0).count();
+  };
+  const unsigned long long bytes = rep->bytes_requested;
+  const unsigned long long half = bytes / 2;  // a multiple of 16
+  HostWindow win;
+
+  auto t0 = clock::now();
+  const hipError_t eh = hipHostMalloc(&win.host, bytes, hipHostMallocDefault);
+  if (eh != hipSuccess) win.host = nullptr;
+  const hipError_t ed =
+      eh == hipSuccess ? win.staging.ensure(bytes) : hipErrorOutOfMemory;
+  rep->alloc_ms = ms_since(t0);
+  if (eh != hipSuccess || ed != hipSuccess) {
+    (void)hipGetLastError();  // the device is fine, the buffers were not there
+    snprintf(rep->error, sizeof(rep->error),
+             "allocated %llu of %llu MiB pinned host, %llu of %llu MiB device",
+             eh == hipSuccess ? bytes >> 20 : 0ull, bytes >> 20,
+             ed == hipSuccess ? bytes >> 20 : 0ull, bytes >> 20);
+    return 0;
+  }
+  uint32_t* const H = (uint32_t*)win.host;
+  void* Hd = nullptr;  // H as the device addresses it
+  CC_CHECK(hipHostGetDevicePointer(&Hd, win.host, 0));
+  void* const D = win.staging.p;
+  HbmMarchResult* const dRes = dev.host.dRes;
+
+  CC_TRY(link_reset(dev, rep));
+  HbmMarchResult cpu = {};
+  cpu.first_bad_offset = ~0ull;
+
+  auto addr = [&](int pass) {
+    return rep->origin + (unsigned long long)pass * HOST_LINK_PASS_STRIDE;
+  };
+  // CPU work on H[at, at + n), timed into host_ms
+  auto fill = [&](int pass, unsigned long long at, unsigned long long n) {
+    const auto t = clock::now();
+    host_pattern_fill(H + at / 4, n / 4, (addr(pass) + at) / 4, (pass + 1) & 1);
+    rep->host_ms += ms_since(t);
+  };
+  auto compare = [&](int pass, unsigned long long at, unsigned long long n) {
+    const auto t = clock::now();
+    host_pattern_compare(H + at / 4, n / 4, (addr(pass) + at) / 4, at,
+                         (pass + 1) & 1, pass, &cpu);
+    rep->host_ms += ms_since(t);
+  };
+  // the detector's wrong number, when this pass and this range hold it
+  auto poison = [&](int pass, unsigned long long at, unsigned long long n) {
+    if (pass == poison_pass && (unsigned long long)poison_offset >= at &&
+        (unsigned long long)poison_offset < at + n)
+      H[poison_offset / 4] ^= 1u;
+  };
+
+  // 1 pull: CPU fill, the shader loads H over the link and checks it
+  fill(1, 0, bytes);
+  poison(1, 0, bytes);
+  CC_TRY(timed_ms(dev, rep, &rep->pull_ms, [&] {
+    launch_link(0, -1, Hd, bytes, addr(1), 0, dRes, 1);
+    return 0;
+  }));
+  CC_CHECK(hipGetLastError());
+  rep->passes = 1;
+
+  // 2 push: the shader stores ~p into H over the link, the CPU checks it
+  CC_TRY(timed_ms(dev, rep, &rep->push_ms, [&] {
+    launch_link(-1, 1, Hd, bytes, addr(2), 0, dRes, 2);
+    return 0;
+  }));
+  CC_CHECK(hipGetLastError());
+  poison(2, 0, bytes);
+  compare(2, 0, bytes);
+  rep->passes = 2;
+
+  // 3 h2d: CPU fill, the runtime copies H -> D, march_step checks D
+  fill(3, 0, bytes);
+  poison(3, 0, bytes);
+  CC_TRY(timed_ms(dev, rep, &rep->h2d_ms, [&] {
+    CC_CHECK(hipMemcpyAsync(D, H, bytes, hipMemcpyHostToDevice, 0));
+    return 0;
+  }));
+  launch_march(0, -1, D, bytes, addr(3), 0, dRes, 3, cu_count);
+  CC_CHECK(hipGetLastError());
+  CC_CHECK(hipDeviceSynchronize());
+  rep->passes = 3;
+
+  // 4 d2h: march_step fills D with ~p, the runtime copies D -> H, the
+  // CPU checks H
+  launch_march(-1, 1, D, bytes, addr(4), 0, dRes, 4, cu_count);
+  CC_CHECK(hipGetLastError());
+  CC_TRY(timed_ms(dev, rep, &rep->d2h_ms, [&] {
+    CC_CHECK(hipMemcpyAsync(H, D, bytes, hipMemcpyDeviceToHost, 0));
+    return 0;
+  }));
+  poison(4, 0, bytes);
+  compare(4, 0, bytes);
+  rep->passes = 4;
+
+  // 5 duplex: one launch pulls the lower half and pushes the upper one
+  fill(5, 0, half);
+  poison(5, 0, half);
+  CC_TRY(timed_ms(dev, rep, &rep->duplex_ms, [&] {
+    const uint32_t nlo = (uint32_t)(half / 16);
+    const uint32_t nhi = (uint32_t)((bytes - half) / 16);
+    // each role gets half of the grid a one-way pass would have
+    const uint32_t per_role = host_link_blocks(nhi, HOST_LINK_MAX_BLOCKS / 2);
+    hipLaunchKernelGGL(link_duplex<>, dim3(2 * per_role),
+                       dim3(HOST_LINK_THREADS), 0, 0, (u32x4*)Hd, nlo, nhi,
+                       addr(5) / 4, 0ull, dRes, 5);
+    return 0;
+  }));
+  CC_CHECK(hipGetLastError());
+  poison(5, half, bytes - half);
+  compare(5, half, bytes - half);
+  rep->passes = 5;
+
+  CC_TRY(link_collect(dev, rep, cpu));
+  rep->bytes_tested = (long long)bytes;
+  rep->pull_gbps = link_gbps(bytes, rep->pull_ms);
+  rep->push_gbps = link_gbps(bytes, rep->push_ms);
+  rep->h2d_gbps = link_gbps(bytes, rep->h2d_ms);
+  rep->d2h_gbps = link_gbps(bytes, rep->d2h_ms);
+  rep->duplex_pull_gbps = link_gbps(half, rep->duplex_ms);
+  rep->duplex_push_gbps = link_gbps(bytes - half, rep->duplex_ms);
+  return 0;
+}
+
+// One direction over caller-owned host memory `ptr` (device address
+// `dptr`), for cc_host_step. engine 0: link_pull / link_push on the
+// mapped range. engine 1: the runtime's copy to or from a staging buffer
+// that lives for the call, with march_step on the staging buffer; only
+// the copy is timed.
+static int probe_host_step(DeviceCtx& dev, CcHostReport* rep, HostWindow& win,
+                           void* ptr, void* dptr, int check, int write,
+                           int cu_count) {
+  const unsigned long long bytes = rep->bytes_requested;
+  HbmMarchResult* const dRes = dev.host.dRes;
+  CC_TRY(link_reset(dev, rep));
+  double* ms;
+  double* gbps;
+  if (rep->engine == 0) {
+    ms = check >= 0 ? &rep->pull_ms : &rep->push_ms;
+    gbps = check >= 0 ? &rep->pull_gbps : &rep->push_gbps;
+    CC_TRY(timed_ms(dev, rep, ms, [&] {
+      launch_link(check, write, dptr, bytes, rep->origin, 0, dRes, 0);
+      return 0;
+    }));
+    CC_CHECK(hipGetLastError());
+  } else {
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipError_t e = win.staging.ensure(bytes);
+    rep->alloc_ms = std::chrono::duration<double, std::milli>(
+                        std::chrono::steady_clock::now() - t0)
+                        .count();
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      snprintf(rep->error, sizeof(rep->error),
+               "allocated 0 of %llu bytes of device staging", bytes);
+      return 0;
+    }
+    void* const D = win.staging.p;
+    if (check >= 0) {
+      ms = &rep->h2d_ms, gbps = &rep->h2d_gbps;
+      CC_TRY(timed_ms(dev, rep, ms, [&] {
+        CC_CHECK(hipMemcpyAsync(D, ptr, bytes, hipMemcpyHostToDevice, 0));
+        return 0;
+      }));
+      launch_march(check, -1, D, bytes, rep->origin, 0, dRes, 0, cu_count);
+      CC_CHECK(hipGetLastError());
+    } else {
+      ms = &rep->d2h_ms, gbps = &rep->d2h_gbps;
+      launch_march(-1, write, D, bytes, rep->origin, 0, dRes, 0, cu_count);
+      CC_CHECK(hipGetLastError());
+      CC_TRY(timed_ms(dev, rep, ms, [&] {
+        CC_CHECK(hipMemcpyAsync(ptr, D, bytes, hipMemcpyDeviceToHost, 0));
+        return 0;
+      }));
+    }
+    CC_CHECK(hipDeviceSynchronize());
+  }
+  HbmMarchResult none = {};
+  none.first_bad_offset = ~0ull;
+  CC_TRY(link_collect(dev, rep, none));
+  *gbps = link_gbps(bytes, *ms);
+  rep->passes = 1;
+  rep->bytes_tested = (long long)bytes;
+  return 0;
+}

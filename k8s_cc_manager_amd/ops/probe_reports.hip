@@ -1,4 +1,4 @@
-// The four report structs of the C API. Their layouts are frozen:
+// The five report structs of the C API. Their layouts are frozen:
 // ops/attest.py mirrors each with a ctypes.Structure, and a drifted
 // mirror reads fields from wrong offsets.
 
@@ -97,12 +97,42 @@ struct CcHbmReport {
   char error[256];
 };
 
+// Report of the opt-in host-link leg (cc_host_link), of one direction on
+// a caller's host buffer (cc_host_step) and of the CPU fill / compare on
+// its own (cc_host_pattern). Offsets are bytes from the start of the
+// window; a record is {offset, expected, got, pass} of one wrong word,
+// whether a kernel or the CPU found it.
+struct CcHostReport {
+  int device;                // -1 from cc_host_pattern
+  int engine;                // cc_host_step: 0 shader, 1 copy engine
+  int passes;                // passes that ran over the whole window (5)
+  int n_bad;                 // records filled, <= 16
+  long long bytes_requested;
+  long long bytes_tested;    // 0 when the buffers could not be allocated
+  unsigned long long origin;
+  unsigned long long mismatch_words;
+  unsigned long long first_bad_offset;  // all ones when clean
+  unsigned long long bad_offset[16];
+  unsigned int bad_expected[16];
+  unsigned int bad_got[16];
+  int bad_pass[16];          // 1..5; 0 from cc_host_step / cc_host_pattern
+  // device events around the launch or the copy alone, per pass
+  double pull_ms, push_ms, h2d_ms, d2h_ms, duplex_ms;
+  double pull_gbps, push_gbps, h2d_gbps, d2h_gbps;
+  double duplex_pull_gbps, duplex_push_gbps;  // half the window each
+  double host_ms;            // CPU fill and compare, host clock: not link time
+  double alloc_ms;           // host clock around the two allocations
+  int ok;
+  char error[256];
+};
+
 }  // extern "C"
 
 static_assert(sizeof(CcAttestReport) == 504, "CcAttestReport layout is frozen");
 static_assert(sizeof(CcMxReport) == 320, "CcMxReport layout is frozen");
 static_assert(sizeof(CcSweepReport) == 392, "CcSweepReport layout is frozen");
 static_assert(sizeof(CcHbmReport) == 704, "CcHbmReport layout is frozen");
+static_assert(sizeof(CcHostReport) == 744, "CcHostReport layout is frozen");
 
 // Error text of a call that has no report (cc_cu_sweep_gold).
 struct ErrorText {
