@@ -40,8 +40,14 @@ def available() -> bool:
         return False
 
 
-def pci_scan(root: str = "/sys/bus/pci/devices") -> List[Dict[str, Any]]:
-    return _load().pci_scan(root)
+def pci_scan(root: str = "/sys/bus/pci/devices",
+             kfd_root: str = "/sys/class/kfd/kfd/topology/nodes",
+             ) -> List[Dict[str, Any]]:
+    """AMD GPUs / accelerators under ``root``. ``driver`` is the name the
+    device's ``driver`` link points to; where sysfs shows no link (a guest
+    with a filtered sysfs) it is ``amdgpu`` when KFD under ``kfd_root``
+    lists a GPU node at the device's PCI address, else empty."""
+    return _load().pci_scan(root, kfd_root)
 
 
 def pci_config_read(bdf: str, offset: int = 0, size: int = 64,

@@ -7,7 +7,9 @@
 //
 //   pci_scan()        — enumerate AMD accelerators/GPUs from PCI config
 //                       space (vendor 0x1002, class 0x0380xx/0x0300xx),
-//                       reading each device's config header directly;
+//                       reading each device's config header directly; the
+//                       bound driver from the `driver` link, or from KFD
+//                       where sysfs shows no link;
 //   pci_config_read() — raw config-space bytes for capability checks;
 //   pci_reset()       — sysfs function-level reset (privileged path);
 //   kfd_version()     — AMDKFD_IOC_GET_VERSION ioctl on /dev/kfd: the
@@ -27,6 +29,7 @@
 #include <unistd.h>
 
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <fstream>
 #include <sstream>
@@ -66,7 +69,39 @@ long read_hex(const std::string& path, long fallback = -1) {
 // PCI
 // ---------------------------------------------------------------------------
 
-static std::vector<py::dict> pci_scan(const std::string& root) {
+// True when KFD lists a GPU node at this PCI address. Only amdgpu
+// registers devices with KFD, so such a node names the bound driver where
+// sysfs has no `driver` link (a guest whose sysfs is filtered). A node's
+// location_id is bus << 8 | devfn, its domain the PCI domain.
+static bool kfd_has_gpu_at(const std::string& kfd_root,
+                           const std::string& bdf) {
+  unsigned domain, bus, dev, fn;
+  if (sscanf(bdf.c_str(), "%x:%x:%x.%x", &domain, &bus, &dev, &fn) != 4)
+    return false;
+  const long long location = (bus << 8) | (dev << 3) | fn;
+  DIR* dir = opendir(kfd_root.c_str());
+  if (!dir) return false;
+  bool found = false;
+  struct dirent* ent;
+  while (!found && (ent = readdir(dir)) != nullptr) {
+    std::ifstream f(kfd_root + "/" + ent->d_name + "/properties");
+    if (!f) continue;
+    long long simd = 0, node_domain = -1, node_location = -1, value;
+    std::string key;
+    while (f >> key >> value) {
+      if (key == "simd_count") simd = value;
+      if (key == "domain") node_domain = value;
+      if (key == "location_id") node_location = value;
+    }
+    found = simd > 0 && node_domain == (long long)domain &&
+            node_location == location;
+  }
+  closedir(dir);
+  return found;
+}
+
+static std::vector<py::dict> pci_scan(const std::string& root,
+                                      const std::string& kfd_root) {
   std::vector<py::dict> out;
   DIR* dir = opendir(root.c_str());
   if (!dir) return out;
@@ -91,7 +126,7 @@ static std::vector<py::dict> pci_scan(const std::string& root) {
     d["driver"] = [&]() -> std::string {
       char buf[512];
       ssize_t n = readlink((base + "/driver").c_str(), buf, sizeof(buf) - 1);
-      if (n <= 0) return "";
+      if (n <= 0) return kfd_has_gpu_at(kfd_root, bdf) ? "amdgpu" : "";
       buf[n] = 0;
       std::string s(buf);
       auto pos = s.rfind('/');
@@ -182,7 +217,8 @@ static std::vector<py::dict> kfd_topology(const std::string& root) {
 
 PYBIND11_MODULE(_devnative, m) {
   m.doc() = "AMD CC manager native device library (PCI sysfs + /dev/kfd)";
-  m.def("pci_scan", &pci_scan, py::arg("root") = "/sys/bus/pci/devices");
+  m.def("pci_scan", &pci_scan, py::arg("root") = "/sys/bus/pci/devices",
+        py::arg("kfd_root") = "/sys/class/kfd/kfd/topology/nodes");
   m.def("pci_config_read", &pci_config_read, py::arg("bdf"),
         py::arg("offset") = 0, py::arg("size") = 64,
         py::arg("root") = "/sys/bus/pci/devices");

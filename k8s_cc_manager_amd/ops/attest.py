@@ -759,8 +759,9 @@ def host_step(device_index: int, ptr: int, nbytes: int, origin: int = 0,
     pattern on the device and lands it in the buffer; exactly one of the
     two, the other -1. ``engine`` 0 is the shader on the mapped range
     (link_pull / link_push), 1 the runtime's copy path with a device
-    staging buffer. The range is page-locked for the call unless it
-    already is. ``ptr`` 16-aligned, ``nbytes`` a positive multiple of 16
+    staging buffer. A page-locked range is used as it is; any other goes
+    through a pinned window of the same size that lives for the call.
+    ``ptr`` 16-aligned, ``nbytes`` a positive multiple of 16
     of at most 1 GiB; anything else raises with rc=-2. Mismatches are
     reported, not raised."""
     c = _CHostReport()

@@ -568,9 +568,12 @@ int cc_host_link(int device, long long mib, unsigned long long origin,
 // (engine 0) or by a copy into a staging buffer and march_step there
 // (engine 1). write: the pattern is generated on the device and lands in
 // the caller's memory, by link_push (engine 0) or by a march_step fill
-// of the staging buffer and a copy (engine 1). The range is page-locked
-// for the call with hipHostRegister unless it already is, and
-// unregistered on every path out; device and managed memory are refused.
+// of the staging buffer and a copy (engine 1). A range that is already
+// page-locked is used as it is. Any other goes through a hipHostMalloc
+// window of the same size that lives for the call: the CPU copies the
+// range into it before a check and out of it after a write, and the link
+// traffic is the window's. (Not hipHostRegister: a virtualised device
+// refuses it.) Device and managed memory are refused.
 // host_ptr 16-aligned, nbytes a positive multiple of 16 of at most
 // 1 GiB, origin as for cc_hbm_step; anything else returns -2 before the
 // device is touched. Bytes outside the range are never written. Offsets
@@ -613,14 +616,25 @@ int cc_host_step(int device, void* host_ptr, long long nbytes,
   CC_CHECK(dev.events());
   CC_CHECK(dev.host.acquire());
   HostWindow win;
+  void* linked = host_ptr;  // the page-locked range the link sees
   if (!pinned) {
-    CC_CHECK(hipHostRegister(host_ptr, nbytes, hipHostRegisterMapped));
-    win.registered = host_ptr;
+    if (hipHostMalloc(&win.host, nbytes, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();  // the device is fine, the window was not there
+      win.host = nullptr;
+      snprintf(rep->error, sizeof(rep->error),
+               "allocated 0 of %lld bytes of pinned host window", nbytes);
+      return 0;
+    }
+    linked = win.host;
+    if (check >= 0) __builtin_memcpy(linked, host_ptr, (size_t)nbytes);
   }
   void* dptr = nullptr;
-  CC_CHECK(hipHostGetDevicePointer(&dptr, host_ptr, 0));
-  CC_TRY(probe_host_step(dev, rep, win, host_ptr, dptr, check, write,
+  CC_CHECK(hipHostGetDevicePointer(&dptr, linked, 0));
+  CC_TRY(probe_host_step(dev, rep, win, linked, dptr, check, write,
                          prop.multiProcessorCount));
+  // every path that reaches here has synchronised after its last store
+  if (!pinned && write >= 0 && rep->passes == 1)
+    __builtin_memcpy(host_ptr, linked, (size_t)nbytes);
   rep->ok = rep->passes == 1 && rep->mismatch_words == 0;
   return 0;
 }

@@ -1,7 +1,6 @@
 // Host link: the shader side of the verified PCIe passes. The kernels
-// run on a mapped, page-locked host buffer (hipHostMalloc or
-// hipHostRegister memory, never managed or pageable), so every load and
-// store below crosses the link.
+// run on a mapped, page-locked host buffer (hipHostMalloc memory, never
+// managed or pageable), so every load and store below crosses the link.
 //
 //   link_pull<PHASE>   every 16-byte vector of the buffer is loaded over
 //                      the link and compared with phase PHASE; nothing is

@@ -156,8 +156,7 @@ struct HbmCtx {
 };
 
 // The host-link leg (cc_host_link, cc_host_step): only the device result
-// block. The pinned window, a registration and the staging buffer belong
-// to the call.
+// block. The pinned window and the staging buffer belong to the call.
 struct HostCtx {
   DevBuf<HbmMarchResult> dRes;
   hipError_t acquire() { return dRes.ensure(sizeof(HbmMarchResult)); }

@@ -449,16 +449,13 @@ static int probe_hbm_march(DeviceCtx& dev, CcHbmReport* rep, int cu_count,
   return 0;
 }
 
-// The buffers of one host-link call: a pinned, mapped host window, a
-// device staging buffer, and a registration of caller-owned memory. All
-// are released on every path out.
+// The buffers of one host-link call: a pinned, mapped host window and a
+// device staging buffer. Both are released on every path out.
 struct HostWindow {
-  void* host = nullptr;        // hipHostMalloc
-  void* registered = nullptr;  // hipHostRegister of the caller's range
+  void* host = nullptr;  // hipHostMalloc
   DevBuf<u32x4> staging;
   ~HostWindow() {
     if (host) (void)hipHostFree(host);
-    if (registered) (void)hipHostUnregister(registered);
     staging.release();
   }
 };
@@ -650,7 +647,7 @@ static int probe_host_link(DeviceCtx& dev, CcHostReport* rep, int cu_count,
   return 0;
 }
 
-// One direction over caller-owned host memory `ptr` (device address
+// One direction over page-locked host memory `ptr` (device address
 // `dptr`), for cc_host_step. engine 0: link_pull / link_push on the
 // mapped range. engine 1: the runtime's copy to or from a staging buffer
 // that lives for the call, with march_step on the staging buffer; only

@@ -48,6 +48,36 @@ def test_pci_scan_filters_amd_gpus(fake_sysfs):
     assert accel["has_reset"] is True
 
 
+def test_pci_scan_driver_from_link_or_kfd(fake_sysfs, tmp_path):
+    """The bound driver is the `driver` link's target; a device without
+    the link is amdgpu's exactly when KFD lists a GPU node at its PCI
+    address (domain, bus << 8 | devfn)."""
+    drivers = tmp_path / "drivers"
+    (drivers / "vfio-pci").mkdir(parents=True)
+    (fake_sysfs / "0000:1b:00.0" / "driver").symlink_to(drivers / "vfio-pci")
+    nodes = tmp_path / "nodes"
+    for node, props in {
+        "0": "cpu_cores_count 16\nsimd_count 0\ndomain 0\nlocation_id 0\n",
+        "1": "simd_count 1024\ndomain 0\nlocation_id %d\n" % 0x0A00,
+        # a GPU at 0001:1b:00.0: another domain than the linked device's
+        "2": "simd_count 1024\ndomain 1\nlocation_id %d\n" % 0x1B00,
+    }.items():
+        (nodes / node).mkdir(parents=True)
+        (nodes / node / "properties").write_text(props)
+
+    def drivers_with(kfd_root):
+        found = native.pci_scan(root=str(fake_sysfs), kfd_root=str(kfd_root))
+        return {e["bdf"]: e["driver"] for e in found}
+
+    assert drivers_with(nodes) == {"0000:0a:00.0": "amdgpu",
+                                   "0000:1b:00.0": "vfio-pci"}
+    assert drivers_with(tmp_path / "nokfd") == {"0000:0a:00.0": "",
+                                                "0000:1b:00.0": "vfio-pci"}
+    (fake_sysfs / "0000:1b:00.0" / "driver").unlink()
+    assert drivers_with(nodes) == {"0000:0a:00.0": "amdgpu",
+                                   "0000:1b:00.0": ""}
+
+
 def test_pci_config_read(fake_sysfs):
     raw = native.pci_config_read("0000:0a:00.0", 0, 4, root=str(fake_sysfs))
     vendor, device = struct.unpack("<HH", raw)

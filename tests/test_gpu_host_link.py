@@ -1,8 +1,8 @@
 """Host-link leg on a real MI355X: one direction at a time on numpy
 buffers against a numpy model of the pattern (both engines, sentinels on
 each side), the five-pass leg clean and with a word poisoned in every
-pass, the refusals, the neighbouring legs and the registration that must
-not leak.
+pass, the refusals, the neighbouring legs and the pinning that must not
+leak.
 
 Pattern (docs/KERNELS.md, "Host link"): the HBM march's word at logical
 byte address origin + k * 2^40 + offset for pass k, phase 0 in passes 1,
@@ -253,8 +253,9 @@ def test_neighbouring_legs_unaffected(attest):
 
 
 def test_registration_does_not_leak(attest):
-    """host_step page-locks ordinary memory for the call only: the same
-    buffer registers again, in either engine and after a mismatch."""
+    """What host_step pins for ordinary memory lives for the call only:
+    the same buffer goes through again, in either engine and after a
+    mismatch."""
     nbytes = 4096 + 16
     g = Guarded(nbytes)
     for engine in (0, 1, 0):
@@ -267,7 +268,8 @@ def test_registration_does_not_leak(attest):
 
 def test_pinned_memory_is_used_as_it_is(attest):
     """A buffer that is already page-locked (torch's pinned allocator) is
-    not registered again and stays pinned afterwards."""
+    the range the link sees, with no window in between, and stays pinned
+    afterwards."""
     t = torch.empty(MIB // 4, dtype=torch.int32).pin_memory()
     for engine in ENGINES:
         assert attest.host_step(0, t.data_ptr(), MIB, write=1,
