@@ -427,6 +427,9 @@ _BINDINGS = {
     "cc_mfma_gemm_mxfp4": (_INT, _MX_GEMM),
     "cc_ref_gemm_mxfp4_f32": (_INT, _MX_GEMM),
     "cc_attest_mxfp4": (_INT, [_INT, _INT, ctypes.POINTER(_CMxReport)]),
+    "cc_mfma_gemm_mxfp6": (_INT, _MX_GEMM + [_INT]),
+    "cc_ref_gemm_mxfp6_f32": (_INT, _MX_GEMM + [_INT]),
+    "cc_attest_mxfp6": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CMxReport)]),
     "cc_mx_report_sizeof": (_INT, []),
     "cc_cu_sweep": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CSweepReport)]),
     "cc_cu_sweep_gold": (_INT, [_INT, _INT, ctypes.POINTER(ctypes.c_float)]),
@@ -550,6 +553,53 @@ def attest_mxfp4(device_index: int, gemm_dim: int = 1024) -> MxReport:
     logger.info(
         "attested device %d: mxfp4 GEMM %.1f TF/s (%dx%dx%d), bitwise ok",
         rep.device,
+        rep.mx_tflops,
+        rep.mx_dim,
+        rep.mx_dim,
+        rep.mx_dim,
+    )
+    return rep
+
+
+# fp6 element formats by name; the numbers are the hardware's format
+# selector (cbsz / blgp), which the library takes as they are
+FP6_FORMATS = {"e2m3": 2, "e3m2": 3}
+
+
+def _fp6_fmt(fmt) -> int:
+    """"e2m3" / "e3m2" or a number; a number goes to the library as it
+    is, which refuses anything but 2 and 3 with -2."""
+    if isinstance(fmt, str):
+        if fmt not in FP6_FORMATS:
+            raise AttestationError(f"unknown fp6 format {fmt!r}")
+        return FP6_FORMATS[fmt]
+    return int(fmt)
+
+
+def attest_mxfp6(device_index: int, gemm_dim: int = 1024,
+                 fmt="e2m3") -> MxReport:
+    """Run the MXFP6 probe on one GPU for one element format ("e2m3" /
+    "e3m2" or 2 / 3): the fp6 MFMA GEMM with real E8M0 block scales
+    against the VALU reference, bitwise. Raises on failure. gemm_dim
+    below 128 rounds up to 128, otherwise down to a multiple."""
+    lib = _load()
+    c = _CMxReport()
+    code = _fp6_fmt(fmt)
+    rc = lib.cc_attest_mxfp6(device_index, gemm_dim, code, ctypes.byref(c))
+    rep = MxReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"device {device_index}: mxfp6 probe runtime error rc={rc}: {rep.error}"
+        )
+    if not rep.ok:
+        raise AttestationError(
+            f"device {device_index}: mxfp6 fmt {code} attestation FAILED "
+            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
+        )
+    logger.info(
+        "attested device %d: mxfp6 fmt %d GEMM %.1f TF/s (%dx%dx%d), bitwise ok",
+        rep.device,
+        code,
         rep.mx_tflops,
         rep.mx_dim,
         rep.mx_dim,
@@ -952,6 +1002,9 @@ def attest_device_by_bdf(device) -> dict:
     mx = None
     if os.environ.get("CC_ATTEST_MXFP4", "0") == "1":
         mx = attest_mxfp4(idx, gemm_dim=gemm_dim)
+    mx6 = None
+    if os.environ.get("CC_ATTEST_MXFP6", "0") == "1":
+        mx6 = [attest_mxfp6(idx, gemm_dim=gemm_dim, fmt=f) for f in FP6_FORMATS]
     sweep = None
     if os.environ.get("CC_ATTEST_CU_SWEEP", "0") == "1":
         sweep = sweep_compute_units(idx)
@@ -991,6 +1044,9 @@ def attest_device_by_bdf(device) -> dict:
     if mx is not None:
         summary["mxfp4_tflops"] = round(mx.mx_tflops, 1)
         summary["mxfp4_bitwise_ok"] = mx.mx_max_abs_err == 0.0
+    if mx6 is not None:
+        summary["mxfp6_tflops"] = round(min(r.mx_tflops for r in mx6), 1)
+        summary["mxfp6_bitwise_ok"] = all(r.mx_max_abs_err == 0.0 for r in mx6)
     if sweep is not None:
         summary["cu_sweep"] = f"{sweep.units_seen}/{sweep.units_expected}"
         summary["cu_sweep_ok"] = sweep.ok
@@ -1081,3 +1137,25 @@ def ref_gemm_mxfp4_f32(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
     ldexpf scales, no MFMA): any M and N, K a multiple of 32."""
     _gemm_call("cc_ref_gemm_mxfp4_f32", "ref_gemm_mxfp4_f32",
                device_index, a_ptr, sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k)
+
+
+def mfma_gemm_mxfp6(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
+                    sb_ptr: int, c_ptr: int, m: int, n: int, k: int,
+                    fmt="e2m3") -> None:
+    """MXFP6 GEMM, the convention of :func:`mfma_gemm_mxfp4` with 6-bit
+    elements: fmt "e2m3" (2) or "e3m2" (3) for both operands. A[M,K] and
+    Bt[N,K] hold 3K/4 bytes per row; every 32-element block is 24 bytes
+    read as one little-endian number, element j in bits 6j..6j+5. SA and
+    SB uint8 E8M0 [rows, K/32]. M,N and K multiples of 128, 16-byte
+    aligned pointers; anything else raises with rc=-2."""
+    _gemm_call("cc_mfma_gemm_mxfp6", "mfma_gemm_mxfp6", device_index, a_ptr,
+               sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k, _fp6_fmt(fmt))
+
+
+def ref_gemm_mxfp6_f32(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
+                       sb_ptr: int, c_ptr: int, m: int, n: int, k: int,
+                       fmt="e2m3") -> None:
+    """VALU reference of :func:`mfma_gemm_mxfp6` (integer field extraction
+    and decode, ldexpf scales, no MFMA): any M and N, K a multiple of 32."""
+    _gemm_call("cc_ref_gemm_mxfp6_f32", "ref_gemm_mxfp6_f32", device_index,
+               a_ptr, sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k, _fp6_fmt(fmt))

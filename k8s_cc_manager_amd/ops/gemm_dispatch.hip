@@ -209,3 +209,30 @@ static void launch_ref_mxfp4(const void* A, const void* SA, const void* Bt,
                      (const unsigned char*)Bt, (const unsigned char*)SB,
                      (float*)C, M, N, K);
 }
+
+// Launch the MXFP6 MFMA GEMM (no sync); fmt 2 = e2m3, 3 = e3m2. -2 for
+// any other fmt, a shape that does not fit the 128x128x128 tile or
+// operands that are not 16-byte aligned.
+static int launch_mxfp6(int fmt, const void* A, const void* SA, const void* Bt,
+                        const void* SB, void* C, int M, int N, int K) {
+  if (fmt != 2 && fmt != 3) return -2;
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BK6) return -2;
+  if ((((uintptr_t)A | (uintptr_t)Bt | (uintptr_t)SA | (uintptr_t)SB |
+        (uintptr_t)C) & 15) != 0)
+    return -2;
+  auto kernel = fmt == 2 ? mfma_gemm_mxfp6_128<2> : mfma_gemm_mxfp6_128<3>;
+  hipLaunchKernelGGL(kernel, dim3(N / BN, M / BM), dim3(256), 0, 0,
+                     (const char*)A, (const unsigned char*)SA, (const char*)Bt,
+                     (const unsigned char*)SB, (float*)C, M, N, K);
+  return 0;
+}
+
+static void launch_ref_mxfp6(int fmt, const void* A, const void* SA,
+                             const void* Bt, const void* SB, void* C, int M,
+                             int N, int K) {
+  dim3 block(16, 16), grid((N + 15) / 16, (M + 15) / 16);
+  auto kernel = fmt == 2 ? ref_gemm_mxfp6_f32<2> : ref_gemm_mxfp6_f32<3>;
+  hipLaunchKernelGGL(kernel, grid, block, 0, 0, (const uint32_t*)A,
+                     (const unsigned char*)SA, (const uint32_t*)Bt,
+                     (const unsigned char*)SB, (float*)C, M, N, K);
+}

@@ -124,6 +124,35 @@ struct MxCtx {
   }
 };
 
+// The MXFP6 leg (cc_attest_mxfp6), same rules as MainCtx, keyed by
+// (dim, fmt): the fill and so the cached reference depend on the format.
+struct Mx6Ctx {
+  int dim = 0;
+  int fmt = 0;
+  int ref_valid = 0;
+  DevBuf<unsigned char> dA, dB;    // packed fp6, 3/4 byte per element
+  DevBuf<unsigned char> dSA, dSB;  // e8m0
+  DevBuf<float> dC, dRef, dErr;
+  DevBuf<unsigned long long> dSum;
+
+  hipError_t acquire(int D, int F) {
+    if (dim == D && fmt == F) return hipSuccess;
+    *this = Mx6Ctx{};
+    const size_t n = (size_t)D * D;
+    hipError_t e;
+    if ((e = dA.ensure(n / 4 * 3)) || (e = dB.ensure(n / 4 * 3)) ||
+        (e = dSA.ensure(n / 32)) || (e = dSB.ensure(n / 32)) ||
+        (e = dC.ensure(n * sizeof(float))) ||
+        (e = dRef.ensure(n * sizeof(float))) ||
+        (e = dErr.ensure(sizeof(float))) ||
+        (e = dSum.ensure(sizeof(unsigned long long))))
+      return e;
+    dim = D;
+    fmt = F;
+    return hipSuccess;
+  }
+};
+
 // The compute-unit sweep (cc_cu_sweep): fixed sizes, allocated once.
 struct SweepCtx {
   DevBuf<unsigned> dSweepTab;
@@ -167,6 +196,7 @@ struct DeviceCtx {
   MainCtx main;
   PeerCtx peer;
   MxCtx mx;
+  Mx6Ctx mx6;
   SweepCtx sweep;
   HbmCtx hbm;
   HostCtx host;

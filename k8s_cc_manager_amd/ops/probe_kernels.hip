@@ -129,6 +129,95 @@ __global__ void ref_gemm_mxfp4_f32(const unsigned char* __restrict__ A,
   C[(long)row * N + col] = acc;
 }
 
+// ---------------------------------------------------------------------------
+// MXFP6 leg: fill and the VALU reference (data convention in
+// gemm_fp6.hip). fmt 2 = e2m3, 3 = e3m2.
+// ---------------------------------------------------------------------------
+// The codes of the magnitudes {0, 0.5, 1, 1.5, 2, 3} in each format
+// (e2m3's 0.5 is a subnormal, e3m2's are all normals).
+__device__ __forceinline__ unsigned fp6_exact_code(int fmt, unsigned idx) {
+  return fmt == 2 ? 4u * idx : (0x12100E0C0800ull >> (8 * idx)) & 63u;
+}
+
+// nblocks 24-byte blocks of 32 codes drawn from those magnitudes with
+// both signs (-0 included), one thread per block. With fill_e8m0_lcg's
+// scale bytes every term is a multiple of 2^-4 of at most 36, so every
+// partial sum fits 24 bits in any order while K * 576 < 2^24 (K up to
+// 29,127) and the MFMA and VALU paths must agree bitwise. The other 52
+// codes of each format are the tests' ground, not the gate's.
+__global__ void fill_fp6_exact(uint32_t* __restrict__ out, long nblocks,
+                               uint32_t seed, int fmt) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+  for (; i < nblocks; i += stride) {
+    unsigned long long w[3] = {0, 0, 0};  // 64 bits hold 10 codes and 4 bits
+    for (int j = 0; j < 32; ++j) {
+      uint32_t x = (uint32_t)(i * 32 + j) * 1103515245u + seed * 747796405u +
+                   12345u;
+      x ^= x >> 16;
+      x *= 2654435769u;
+      unsigned r = (x >> 13) % 12u;
+      unsigned long long code = fp6_exact_code(fmt, r % 6u) | (r / 6u) << 5;
+      int bit = 6 * j;
+      w[bit >> 6] |= code << (bit & 63);
+      if ((bit & 63) > 58) w[(bit >> 6) + 1] |= code >> (64 - (bit & 63));
+    }
+    for (int q = 0; q < 3; ++q) {
+      out[i * 6 + 2 * q] = (uint32_t)w[q];
+      out[i * 6 + 2 * q + 1] = (uint32_t)(w[q] >> 32);
+    }
+  }
+}
+
+// the value of an fp6 code as a fixed-point integer: e2m3 times 8
+// (0..60), e3m2 times 16 (0..448), with the sign of bit 5
+template <int FMT>
+__device__ __forceinline__ int fp6_fixed(unsigned code) {
+  constexpr int MB = FMT == 2 ? 3 : 2;  // mantissa bits
+  int e = (code >> MB) & (31 >> MB), m = code & ((1 << MB) - 1);
+  int v = e ? ((1 << MB) + m) << (e - 1) : m;
+  return (code & 32) ? -v : v;
+}
+
+// element j of a 24-byte block held as 6 dwords
+__device__ __forceinline__ unsigned fp6_field(const uint32_t* blk, int j) {
+  int bit = 6 * j, w = bit >> 5;
+  unsigned long long two = blk[w];
+  if (w < 5) two |= (unsigned long long)blk[w + 1] << 32;
+  return (unsigned)(two >> (bit & 31)) & 63u;
+}
+
+// VALU MXFP6 reference GEMM: one thread per C element; per 32-element
+// block the integer products are summed in fp32 in k order, the block
+// sum is scaled with ldexpf, and blocks are added in kb order.
+template <int FMT>
+__global__ void ref_gemm_mxfp6_f32(const uint32_t* __restrict__ A,
+                                   const unsigned char* __restrict__ SA,
+                                   const uint32_t* __restrict__ Bt,
+                                   const unsigned char* __restrict__ SB,
+                                   float* __restrict__ C, int M, int N,
+                                   int K) {
+  int col = blockIdx.x * blockDim.x + threadIdx.x;
+  int row = blockIdx.y * blockDim.y + threadIdx.y;
+  if (row >= M || col >= N) return;
+  const int nkb = K >> 5;
+  const uint32_t* a = A + (long)row * nkb * 6;
+  const uint32_t* b = Bt + (long)col * nkb * 6;
+  const unsigned char* sa = SA + (long)row * nkb;
+  const unsigned char* sb = SB + (long)col * nkb;
+  // the products carry the square of the fixed-point factor
+  constexpr int kFixedLog2 = FMT == 2 ? 6 : 8;
+  float acc = 0.f;
+  for (int kb = 0; kb < nkb; ++kb) {
+    float blk = 0.f;
+    for (int j = 0; j < 32; ++j)
+      blk += (float)(fp6_fixed<FMT>(fp6_field(a + kb * 6, j)) *
+                     fp6_fixed<FMT>(fp6_field(b + kb * 6, j)));
+    acc += ldexpf(blk, (int)sa[kb] + (int)sb[kb] - 254 - kFixedLog2);
+  }
+  C[(long)row * N + col] = acc;
+}
+
 // max |x-y| reduction over n elements -> out[0] (pre-zeroed)
 __global__ void max_abs_diff(const float* __restrict__ x,
                              const float* __restrict__ y, long n,

@@ -254,6 +254,40 @@ static int probe_mxfp4(DeviceCtx& dev, CcMxReport* rep) {
                            dSum, &rep->mx_checksum);
 }
 
+// MXFP6 leg: the exact magnitude set (fill_fp6_exact) and scale bytes
+// {126,127,128} through the 6-bit decoder of ctx.fmt and the block-scale
+// hardware, bitwise against the VALU reference.
+static int probe_mxfp6(DeviceCtx& dev, CcMxReport* rep) {
+  Mx6Ctx& ctx = dev.mx6;
+  const int D = ctx.dim, fmt = ctx.fmt;
+  const long elems = (long)D * D;
+  unsigned char *dA = ctx.dA, *dB = ctx.dB, *dSA = ctx.dSA, *dSB = ctx.dSB;
+  float *dC = ctx.dC, *dRef = ctx.dRef, *dErr = ctx.dErr;
+  unsigned long long* dSum = ctx.dSum;
+  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
+  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
+  // 0x7f7f7f7f: finite and huge, as in probe_mxfp4
+  CC_CHECK(hipMemset(dC, 0x7F, elems * sizeof(float)));
+
+  hipLaunchKernelGGL(fill_fp6_exact, dim3(1024), dim3(256), 0, 0,
+                     (uint32_t*)dA, elems / 32, 1u, fmt);
+  hipLaunchKernelGGL(fill_fp6_exact, dim3(1024), dim3(256), 0, 0,
+                     (uint32_t*)dB, elems / 32, 7u, fmt);
+  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, dSA,
+                     elems / 32, 1u);
+  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, dSB,
+                     elems / 32, 7u);
+
+  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops, [&] {
+    return launch_mxfp6(fmt, dA, dSA, dB, dSB, dC, D, D, D);
+  }));
+  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms, [&] {
+    launch_ref_mxfp6(fmt, dA, dSA, dB, dSB, dRef, D, D, D);
+  }));
+  return compare_read_back(rep, dC, dRef, elems, dErr, &rep->mx_max_abs_err,
+                           dSum, &rep->mx_checksum);
+}
+
 // The golden C images for `rounds`, a constant: computed once per
 // (device, rounds). *ms = 0.0 when the cached images were used. `rep`
 // is whatever holds the error text (a report, or ErrorText).
