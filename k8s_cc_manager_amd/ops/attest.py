@@ -430,6 +430,10 @@ _BINDINGS = {
     "cc_mfma_gemm_mxfp6": (_INT, _MX_GEMM + [_INT]),
     "cc_ref_gemm_mxfp6_f32": (_INT, _MX_GEMM + [_INT]),
     "cc_attest_mxfp6": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CMxReport)]),
+    "cc_mfma_gemm_mxfp8": (_INT, _MX_GEMM + [_INT, _INT]),
+    "cc_ref_gemm_mxfp8_f32": (_INT, _MX_GEMM + [_INT, _INT]),
+    "cc_attest_mxfp8": (_INT, [_INT, _INT, _INT, _INT,
+                               ctypes.POINTER(_CMxReport)]),
     "cc_mx_report_sizeof": (_INT, []),
     "cc_cu_sweep": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CSweepReport)]),
     "cc_cu_sweep_gold": (_INT, [_INT, _INT, ctypes.POINTER(ctypes.c_float)]),
@@ -607,6 +611,61 @@ def attest_mxfp6(device_index: int, gemm_dim: int = 1024,
     )
     return rep
 
+
+# fp8 element formats by name; the numbers are the hardware's format
+# selector (cbsz for A, blgp for B), which the library takes as they are
+FP8_FORMATS = {"e4m3": 0, "e5m2": 1}
+
+
+def _fp8_fmt(fmt) -> int:
+    """"e4m3" / "e5m2" or a number; a number goes to the library as it
+    is, which refuses anything but 0 and 1 with -2."""
+    if isinstance(fmt, str):
+        if fmt not in FP8_FORMATS:
+            raise AttestationError(f"unknown fp8 format {fmt!r}")
+        return FP8_FORMATS[fmt]
+    return int(fmt)
+
+
+def attest_mxfp8(device_index: int, gemm_dim: int = 1024, fmt_a="e4m3",
+                 fmt_b=None) -> MxReport:
+    """Run the MXFP8 probe on one GPU for one format pair ("e4m3" /
+    "e5m2" or 0 / 1 for A and for B; ``fmt_b`` None means A's format): the
+    fp8 MFMA GEMM with real E8M0 block scales against the VALU reference,
+    bitwise. Raises on failure. gemm_dim below 128 rounds up to 128,
+    otherwise down to a multiple."""
+    lib = _load()
+    c = _CMxReport()
+    fa = _fp8_fmt(fmt_a)
+    fb = fa if fmt_b is None else _fp8_fmt(fmt_b)
+    rc = lib.cc_attest_mxfp8(device_index, gemm_dim, fa, fb, ctypes.byref(c))
+    rep = MxReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"device {device_index}: mxfp8 probe runtime error rc={rc}: {rep.error}"
+        )
+    if not rep.ok:
+        raise AttestationError(
+            f"device {device_index}: mxfp8 fmt ({fa}, {fb}) attestation FAILED "
+            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
+        )
+    logger.info(
+        "attested device %d: mxfp8 fmt (%d, %d) GEMM %.1f TF/s (%dx%dx%d), "
+        "bitwise ok",
+        rep.device,
+        fa,
+        fb,
+        rep.mx_tflops,
+        rep.mx_dim,
+        rep.mx_dim,
+        rep.mx_dim,
+    )
+    return rep
+
+
+# the format pairs the attestor hook runs: each decoder on each operand
+# side, and cbsz != blgp in both
+MXFP8_HOOK_PAIRS = (("e4m3", "e5m2"), ("e5m2", "e4m3"))
 
 CU_SWEEP_MAX_ROUNDS = 256  # exactness cap of the sweep's MFMA chains
 
@@ -1005,6 +1064,10 @@ def attest_device_by_bdf(device) -> dict:
     mx6 = None
     if os.environ.get("CC_ATTEST_MXFP6", "0") == "1":
         mx6 = [attest_mxfp6(idx, gemm_dim=gemm_dim, fmt=f) for f in FP6_FORMATS]
+    mx8 = None
+    if os.environ.get("CC_ATTEST_MXFP8", "0") == "1":
+        mx8 = [attest_mxfp8(idx, gemm_dim=gemm_dim, fmt_a=fa, fmt_b=fb)
+               for fa, fb in MXFP8_HOOK_PAIRS]
     sweep = None
     if os.environ.get("CC_ATTEST_CU_SWEEP", "0") == "1":
         sweep = sweep_compute_units(idx)
@@ -1047,6 +1110,9 @@ def attest_device_by_bdf(device) -> dict:
     if mx6 is not None:
         summary["mxfp6_tflops"] = round(min(r.mx_tflops for r in mx6), 1)
         summary["mxfp6_bitwise_ok"] = all(r.mx_max_abs_err == 0.0 for r in mx6)
+    if mx8 is not None:
+        summary["mxfp8_tflops"] = round(min(r.mx_tflops for r in mx8), 1)
+        summary["mxfp8_bitwise_ok"] = all(r.mx_max_abs_err == 0.0 for r in mx8)
     if sweep is not None:
         summary["cu_sweep"] = f"{sweep.units_seen}/{sweep.units_expected}"
         summary["cu_sweep_ok"] = sweep.ok
@@ -1159,3 +1225,28 @@ def ref_gemm_mxfp6_f32(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
     and decode, ldexpf scales, no MFMA): any M and N, K a multiple of 32."""
     _gemm_call("cc_ref_gemm_mxfp6_f32", "ref_gemm_mxfp6_f32", device_index,
                a_ptr, sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k, _fp6_fmt(fmt))
+
+
+def mfma_gemm_mxfp8(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
+                    sb_ptr: int, c_ptr: int, m: int, n: int, k: int,
+                    fmt_a="e4m3", fmt_b=None) -> None:
+    """MXFP8 GEMM, the convention of :func:`mfma_gemm_mxfp4` with one byte
+    per element: fmt_a and fmt_b "e4m3" (0) or "e5m2" (1), chosen
+    independently; ``fmt_b`` None means A's format. A[M,K] and Bt[N,K]
+    uint8 OCP codes, SA and SB uint8 E8M0 [rows, K/32]. M,N and K multiples
+    of 128, 16-byte aligned pointers; anything else raises with rc=-2."""
+    fa = _fp8_fmt(fmt_a)
+    _gemm_call("cc_mfma_gemm_mxfp8", "mfma_gemm_mxfp8", device_index, a_ptr,
+               sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k, fa,
+               fa if fmt_b is None else _fp8_fmt(fmt_b))
+
+
+def ref_gemm_mxfp8_f32(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
+                       sb_ptr: int, c_ptr: int, m: int, n: int, k: int,
+                       fmt_a="e4m3", fmt_b=None) -> None:
+    """VALU reference of :func:`mfma_gemm_mxfp8` (integer field extraction,
+    ldexpf decode and scales, no MFMA): any M and N, K a multiple of 32."""
+    fa = _fp8_fmt(fmt_a)
+    _gemm_call("cc_ref_gemm_mxfp8_f32", "ref_gemm_mxfp8_f32", device_index,
+               a_ptr, sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k, fa,
+               fa if fmt_b is None else _fp8_fmt(fmt_b))

@@ -18,10 +18,15 @@
 //   gemm_fp6.hip       MXFP6 (e2m3 / e3m2, real e8m0 block scales) MFMA
 //                      GEMM: mfma_gemm_mxfp6_128<FMT>, register-staged
 //                      padded-row LDS image;
+//   gemm_mxfp8.hip     MXFP8 (e4m3 / e5m2 per operand, real e8m0 block
+//                      scales) MFMA GEMM: mfma_gemm_mxfp8_128<FA, FB>,
+//                      LDS DMA with the operand's k permutation folded
+//                      into the source address (swz8mx);
 //   probe_kernels.hip  fills, ref_gemm_f32 (plain VALU fp32 GEMM of the
 //                      same inputs: the independent on-device ground
 //                      truth), the MXFP4 fills and ref_gemm_mxfp4_f32,
 //                      fill_fp6_exact and ref_gemm_mxfp6_f32<FMT>,
+//                      fill_fp8_exact and ref_gemm_mxfp8_f32<FA, FB>,
 //                      max-diff, checksum, LDS, HBM, liveness;
 //   cu_sweep.hip       compute-unit sweep: cu_sweep (per-SIMD MFMA chains
 //                      and a whole-LDS march, keyed by the hardware ID
@@ -41,7 +46,7 @@
 //                      a DeviceCtx, timed_ms, read_back, DeviceHop;
 //   host_pattern.hip   the CPU fill and compare of the host-link leg
 //                      (plain C++, no HIP call);
-//   probe_legs.hip     the eleven legs and the steps the GEMM legs share.
+//   probe_legs.hip     the twelve legs and the steps the GEMM legs share.
 //
 // cc_attest_device runs five legs in order:
 //   1. probe_bf16  — production bf16 GEMM dispatch, timed, compared
@@ -59,6 +64,8 @@
 // the MXFP4 GEMM against ref_gemm_mxfp4_f32, bitwise.
 // cc_attest_mxfp6 is its 6-bit counterpart, one format (e2m3 or e3m2)
 // per call: the MXFP6 GEMM against ref_gemm_mxfp6_f32, bitwise.
+// cc_attest_mxfp8 is the 8-bit one, one format pair (e4m3 or e5m2 for A
+// and for B) per call: the MXFP8 GEMM against ref_gemm_mxfp8_f32, bitwise.
 // cc_cu_sweep is another: cu_sweep.hip's matrix-core and whole-LDS
 // self-test on every SIMD of every CU, with the units it reached read
 // from the hardware ID registers.
@@ -84,6 +91,7 @@
 #include "gemm_fp8.hip"
 #include "gemm_fp4.hip"
 #include "gemm_fp6.hip"
+#include "gemm_mxfp8.hip"
 #include "probe_kernels.hip"
 #include "cu_sweep.hip"
 #include "hbm_march.hip"
@@ -341,6 +349,58 @@ int cc_attest_mxfp6(int device, int gemm_dim, int fmt, struct CcMxReport* rep) {
   CC_CHECK(dev.events());
   CC_CHECK(dev.mx6.acquire(D, fmt));
   CC_TRY(probe_mxfp6(dev, rep));
+
+  rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
+  return 0;
+}
+
+// MXFP8 GEMM on caller-provided device buffers (layout in
+// gemm_mxfp8.hip): A[M,K], Bt[N,K] one byte per element, e8m0 SA[M,K/32],
+// SB[N,K/32], fp32 C[M,N]; fmt_a and fmt_b 0 = e4m3, 1 = e5m2, chosen
+// independently. M,N multiples of 128, K of 128; anything else returns -2
+// without launching.
+int cc_mfma_gemm_mxfp8(int device, const void* A, const void* SA,
+                       const void* Bt, const void* SB, void* C, int M, int N,
+                       int K, int fmt_a, int fmt_b) {
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  int rc = launch_mxfp8(fmt_a, fmt_b, A, SA, Bt, SB, C, M, N, K);
+  if (rc != 0) return rc;
+  return (int)hipDeviceSynchronize();
+}
+
+// VALU reference of the same convention: any M and N, K a multiple of 32.
+int cc_ref_gemm_mxfp8_f32(int device, const void* A, const void* SA,
+                          const void* Bt, const void* SB, void* C, int M,
+                          int N, int K, int fmt_a, int fmt_b) {
+  if (M <= 0 || N <= 0 || K <= 0 || K % 32 || (fmt_a != 0 && fmt_a != 1) ||
+      (fmt_b != 0 && fmt_b != 1))
+    return -2;
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  launch_ref_mxfp8(fmt_a, fmt_b, A, SA, Bt, SB, C, M, N, K);
+  return (int)hipDeviceSynchronize();
+}
+
+// The opt-in MXFP8 probe for one format pair. gemm_dim below 128 rounds
+// up to 128, otherwise down to a multiple of 128. The report is
+// CcMxReport, unchanged: the caller knows the formats. rep->ok = 1 iff the
+// MFMA result equals the VALU reference bitwise.
+int cc_attest_mxfp8(int device, int gemm_dim, int fmt_a, int fmt_b,
+                    struct CcMxReport* rep) {
+  CC_TRY(report_begin(rep, device, [&] {
+    if ((fmt_a == 0 || fmt_a == 1) && (fmt_b == 0 || fmt_b == 1)) return 0;
+    snprintf(rep->error, sizeof(rep->error), "fmt_a %d or fmt_b %d is not 0 or 1",
+             fmt_a, fmt_b);
+    return -2;
+  }));
+
+  const int D = gemm_dim < BK8 ? BK8 : (gemm_dim / BK8) * BK8;
+  rep->mx_m = rep->mx_n = rep->mx_k = D;
+
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  DeviceCtx& dev = device_ctx(device);
+  CC_CHECK(dev.events());
+  CC_CHECK(dev.mx8.acquire(D, fmt_a, fmt_b));
+  CC_TRY(probe_mxfp8(dev, rep));
 
   rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
   return 0;

@@ -236,3 +236,37 @@ static void launch_ref_mxfp6(int fmt, const void* A, const void* SA,
                      (const unsigned char*)SA, (const uint32_t*)Bt,
                      (const unsigned char*)SB, (float*)C, M, N, K);
 }
+
+// Launch the MXFP8 MFMA GEMM (no sync); fa / fb 0 = e4m3, 1 = e5m2,
+// chosen independently. -2 for any other format, a shape that does not
+// fit the 128x128x128 tile or operands that are not 16-byte aligned.
+static int launch_mxfp8(int fa, int fb, const void* A, const void* SA,
+                        const void* Bt, const void* SB, void* C, int M, int N,
+                        int K) {
+  if ((fa != 0 && fa != 1) || (fb != 0 && fb != 1)) return -2;
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BK8) return -2;
+  if ((((uintptr_t)A | (uintptr_t)Bt | (uintptr_t)SA | (uintptr_t)SB |
+        (uintptr_t)C) & 15) != 0)
+    return -2;
+  auto kernel = fa == 0 ? (fb == 0 ? mfma_gemm_mxfp8_128<0, 0>
+                                   : mfma_gemm_mxfp8_128<0, 1>)
+                        : (fb == 0 ? mfma_gemm_mxfp8_128<1, 0>
+                                   : mfma_gemm_mxfp8_128<1, 1>);
+  hipLaunchKernelGGL(kernel, dim3(N / BN, M / BM), dim3(256), 0, 0,
+                     (const char*)A, (const unsigned char*)SA, (const char*)Bt,
+                     (const unsigned char*)SB, (float*)C, M, N, K);
+  return 0;
+}
+
+static void launch_ref_mxfp8(int fa, int fb, const void* A, const void* SA,
+                             const void* Bt, const void* SB, void* C, int M,
+                             int N, int K) {
+  dim3 block(16, 16), grid((N + 15) / 16, (M + 15) / 16);
+  auto kernel = fa == 0 ? (fb == 0 ? ref_gemm_mxfp8_f32<0, 0>
+                                   : ref_gemm_mxfp8_f32<0, 1>)
+                        : (fb == 0 ? ref_gemm_mxfp8_f32<1, 0>
+                                   : ref_gemm_mxfp8_f32<1, 1>);
+  hipLaunchKernelGGL(kernel, grid, block, 0, 0, (const unsigned char*)A,
+                     (const unsigned char*)SA, (const unsigned char*)Bt,
+                     (const unsigned char*)SB, (float*)C, M, N, K);
+}

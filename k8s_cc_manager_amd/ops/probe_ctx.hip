@@ -153,6 +153,37 @@ struct Mx6Ctx {
   }
 };
 
+// The MXFP8 leg (cc_attest_mxfp8), same rules as MainCtx, keyed by
+// (dim, fa, fb): the fills and so the cached reference depend on both
+// formats.
+struct Mx8Ctx {
+  int dim = 0;
+  int fa = 0, fb = 0;
+  int ref_valid = 0;
+  DevBuf<unsigned char> dA, dB;    // one byte per element
+  DevBuf<unsigned char> dSA, dSB;  // e8m0
+  DevBuf<float> dC, dRef, dErr;
+  DevBuf<unsigned long long> dSum;
+
+  hipError_t acquire(int D, int FA, int FB) {
+    if (dim == D && fa == FA && fb == FB) return hipSuccess;
+    *this = Mx8Ctx{};
+    const size_t n = (size_t)D * D;
+    hipError_t e;
+    if ((e = dA.ensure(n)) || (e = dB.ensure(n)) ||
+        (e = dSA.ensure(n / 32)) || (e = dSB.ensure(n / 32)) ||
+        (e = dC.ensure(n * sizeof(float))) ||
+        (e = dRef.ensure(n * sizeof(float))) ||
+        (e = dErr.ensure(sizeof(float))) ||
+        (e = dSum.ensure(sizeof(unsigned long long))))
+      return e;
+    dim = D;
+    fa = FA;
+    fb = FB;
+    return hipSuccess;
+  }
+};
+
 // The compute-unit sweep (cc_cu_sweep): fixed sizes, allocated once.
 struct SweepCtx {
   DevBuf<unsigned> dSweepTab;
@@ -197,6 +228,7 @@ struct DeviceCtx {
   PeerCtx peer;
   MxCtx mx;
   Mx6Ctx mx6;
+  Mx8Ctx mx8;
   SweepCtx sweep;
   HbmCtx hbm;
   HostCtx host;

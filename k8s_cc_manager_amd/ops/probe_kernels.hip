@@ -218,6 +218,79 @@ __global__ void ref_gemm_mxfp6_f32(const uint32_t* __restrict__ A,
   C[(long)row * N + col] = acc;
 }
 
+// ---------------------------------------------------------------------------
+// MXFP8 leg: fill and the VALU reference (data convention in
+// gemm_mxfp8.hip). fmt 0 = e4m3, 1 = e5m2.
+// ---------------------------------------------------------------------------
+// n bytes drawn from the magnitudes {0, 0.5, 1, 1.5, 2, 3} with both
+// signs (-0 included): e4m3 bytes 00 30 38 3c 40 44, e5m2 bytes 00 38 3c
+// 3e 40 42. The exactness budget is fill_fp6_exact's: with
+// fill_e8m0_lcg's scale bytes every term is a multiple of 2^-4 of at
+// most 36, so every partial sum fits 24 bits in any order while
+// K * 576 < 2^24 and the MFMA and VALU paths must agree bitwise. The
+// other codes of each format are the tests' ground, not the gate's.
+__global__ void fill_fp8_exact(unsigned char* __restrict__ out, long n,
+                               uint32_t seed, int fmt) {
+  const unsigned long long enc = fmt == 0 ? 0x44403C383000ull : 0x42403E3C3800ull;
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    uint32_t x = (uint32_t)i * 1103515245u + seed * 747796405u + 12345u;
+    x ^= x >> 16;
+    x *= 2654435769u;
+    unsigned r = (x >> 13) % 12u;
+    out[i] = (unsigned char)(((enc >> (8 * (r % 6u))) & 255u) | (r / 6u) << 7);
+  }
+}
+
+// the value of an fp8 code: integer field extraction and ldexpf, no
+// conversion instruction. e4m3: bias 7, NaN at S.1111.111, no Inf; e5m2:
+// bias 15, Inf and NaN at exponent 31 (IEEE rules).
+template <int FMT>
+__device__ __forceinline__ float fp8_value(unsigned code) {
+  constexpr int MB = FMT == 0 ? 3 : 2;  // mantissa bits
+  constexpr int BIAS = FMT == 0 ? 7 : 15;
+  const int e = (code >> MB) & (127 >> MB), m = code & ((1 << MB) - 1);
+  float v;
+  if (FMT == 0 && e == 15 && m == 7)
+    v = __builtin_nanf("");
+  else if (FMT == 1 && e == 31)
+    v = m ? __builtin_nanf("") : __builtin_inff();
+  else
+    v = ldexpf((float)(e ? (1 << MB) + m : m), (e ? e : 1) - BIAS - MB);
+  return (code & 128) ? -v : v;
+}
+
+// VALU MXFP8 reference GEMM: one thread per C element. Products are
+// fp32 (two significands of at most 4 bits: exact); per 32-element block
+// they are summed in k order, the block sum is scaled with ldexpf, and
+// blocks are added in kb order. No fixed-point trick as for fp6: e5m2
+// spans 2^-16 .. 57344.
+template <int FA, int FB>
+__global__ void ref_gemm_mxfp8_f32(const unsigned char* __restrict__ A,
+                                   const unsigned char* __restrict__ SA,
+                                   const unsigned char* __restrict__ Bt,
+                                   const unsigned char* __restrict__ SB,
+                                   float* __restrict__ C, int M, int N,
+                                   int K) {
+  int col = blockIdx.x * blockDim.x + threadIdx.x;
+  int row = blockIdx.y * blockDim.y + threadIdx.y;
+  if (row >= M || col >= N) return;
+  const int nkb = K >> 5;
+  const unsigned char* a = A + (long)row * K;
+  const unsigned char* b = Bt + (long)col * K;
+  const unsigned char* sa = SA + (long)row * nkb;
+  const unsigned char* sb = SB + (long)col * nkb;
+  float acc = 0.f;
+  for (int kb = 0; kb < nkb; ++kb) {
+    float blk = 0.f;
+    for (int j = 0; j < 32; ++j)
+      blk += fp8_value<FA>(a[kb * 32 + j]) * fp8_value<FB>(b[kb * 32 + j]);
+    acc += ldexpf(blk, (int)sa[kb] + (int)sb[kb] - 254);
+  }
+  C[(long)row * N + col] = acc;
+}
+
 // max |x-y| reduction over n elements -> out[0] (pre-zeroed)
 __global__ void max_abs_diff(const float* __restrict__ x,
                              const float* __restrict__ y, long n,

@@ -288,6 +288,40 @@ static int probe_mxfp6(DeviceCtx& dev, CcMxReport* rep) {
                            dSum, &rep->mx_checksum);
 }
 
+// MXFP8 leg: the exact magnitude set (fill_fp8_exact) and scale bytes
+// {126,127,128} through the 8-bit decoders of ctx.fa (A) and ctx.fb (B)
+// and the block-scale hardware, bitwise against the VALU reference.
+static int probe_mxfp8(DeviceCtx& dev, CcMxReport* rep) {
+  Mx8Ctx& ctx = dev.mx8;
+  const int D = ctx.dim, fa = ctx.fa, fb = ctx.fb;
+  const long elems = (long)D * D;
+  unsigned char *dA = ctx.dA, *dB = ctx.dB, *dSA = ctx.dSA, *dSB = ctx.dSB;
+  float *dC = ctx.dC, *dRef = ctx.dRef, *dErr = ctx.dErr;
+  unsigned long long* dSum = ctx.dSum;
+  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
+  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
+  // 0x7f7f7f7f: finite and huge, as in probe_mxfp4
+  CC_CHECK(hipMemset(dC, 0x7F, elems * sizeof(float)));
+
+  hipLaunchKernelGGL(fill_fp8_exact, dim3(2048), dim3(256), 0, 0, dA, elems,
+                     1u, fa);
+  hipLaunchKernelGGL(fill_fp8_exact, dim3(2048), dim3(256), 0, 0, dB, elems,
+                     7u, fb);
+  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, dSA,
+                     elems / 32, 1u);
+  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, dSB,
+                     elems / 32, 7u);
+
+  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops, [&] {
+    return launch_mxfp8(fa, fb, dA, dSA, dB, dSB, dC, D, D, D);
+  }));
+  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms, [&] {
+    launch_ref_mxfp8(fa, fb, dA, dSA, dB, dSB, dRef, D, D, D);
+  }));
+  return compare_read_back(rep, dC, dRef, elems, dErr, &rep->mx_max_abs_err,
+                           dSum, &rep->mx_checksum);
+}
+
 // The golden C images for `rounds`, a constant: computed once per
 // (device, rounds). *ms = 0.0 when the cached images were used. `rep`
 // is whatever holds the error text (a report, or ErrorText).
