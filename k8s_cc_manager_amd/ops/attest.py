@@ -434,6 +434,9 @@ _BINDINGS = {
     "cc_ref_gemm_mxfp8_f32": (_INT, _MX_GEMM + [_INT, _INT]),
     "cc_attest_mxfp8": (_INT, [_INT, _INT, _INT, _INT,
                                ctypes.POINTER(_CMxReport)]),
+    "cc_mfma_gemm_i8": (_INT, _GEMM + [_INT]),
+    "cc_ref_gemm_i8_i32": (_INT, _GEMM),
+    "cc_attest_int8": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CMxReport)]),
     "cc_mx_report_sizeof": (_INT, []),
     "cc_cu_sweep": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CSweepReport)]),
     "cc_cu_sweep_gold": (_INT, [_INT, _INT, ctypes.POINTER(ctypes.c_float)]),
@@ -666,6 +669,56 @@ def attest_mxfp8(device_index: int, gemm_dim: int = 1024, fmt_a="e4m3",
 # the format pairs the attestor hook runs: each decoder on each operand
 # side, and cbsz != blgp in both
 MXFP8_HOOK_PAIRS = (("e4m3", "e5m2"), ("e5m2", "e4m3"))
+
+# the integer MFMA shapes of the INT8 leg by name; the numbers are the
+# kernel's template argument, which the library takes as they are
+INT8_SHAPES = {"32x32x32": 0, "16x16x64": 1}
+
+
+def _i8_shape(shape) -> int:
+    """"32x32x32" / "16x16x64" or a number; a number goes to the library
+    as it is, which refuses anything but 0 and 1 with -2."""
+    if isinstance(shape, str):
+        if shape not in INT8_SHAPES:
+            raise AttestationError(f"unknown int8 MFMA shape {shape!r}")
+        return INT8_SHAPES[shape]
+    return int(shape)
+
+
+def attest_int8(device_index: int, gemm_dim: int = 1024,
+                shape="32x32x32") -> MxReport:
+    """Run the INT8 probe on one GPU for one integer MFMA shape
+    ("32x32x32" / "16x16x64" or 0 / 1): the int8 GEMM over the full byte
+    range against the VALU reference, bitwise on int32. The report is
+    MxReport: ``mx_tflops`` carries TOP/s and ``mx_max_abs_err`` the
+    largest |C - ref|, computed in integers. Raises on failure. gemm_dim
+    below 128 rounds up to 128, otherwise down to a multiple."""
+    lib = _load()
+    c = _CMxReport()
+    code = _i8_shape(shape)
+    rc = lib.cc_attest_int8(device_index, gemm_dim, code, ctypes.byref(c))
+    rep = MxReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"device {device_index}: int8 probe runtime error rc={rc}: {rep.error}"
+        )
+    if not rep.ok:
+        raise AttestationError(
+            f"device {device_index}: int8 shape {code} attestation FAILED "
+            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
+        )
+    logger.info(
+        "attested device %d: int8 shape %d GEMM %.1f TOP/s (%dx%dx%d), "
+        "bitwise ok",
+        rep.device,
+        code,
+        rep.mx_tflops,
+        rep.mx_dim,
+        rep.mx_dim,
+        rep.mx_dim,
+    )
+    return rep
+
 
 CU_SWEEP_MAX_ROUNDS = 256  # exactness cap of the sweep's MFMA chains
 
@@ -1068,6 +1121,9 @@ def attest_device_by_bdf(device) -> dict:
     if os.environ.get("CC_ATTEST_MXFP8", "0") == "1":
         mx8 = [attest_mxfp8(idx, gemm_dim=gemm_dim, fmt_a=fa, fmt_b=fb)
                for fa, fb in MXFP8_HOOK_PAIRS]
+    i8 = None
+    if os.environ.get("CC_ATTEST_INT8", "0") == "1":
+        i8 = [attest_int8(idx, gemm_dim=gemm_dim, shape=s) for s in INT8_SHAPES]
     sweep = None
     if os.environ.get("CC_ATTEST_CU_SWEEP", "0") == "1":
         sweep = sweep_compute_units(idx)
@@ -1113,6 +1169,9 @@ def attest_device_by_bdf(device) -> dict:
     if mx8 is not None:
         summary["mxfp8_tflops"] = round(min(r.mx_tflops for r in mx8), 1)
         summary["mxfp8_bitwise_ok"] = all(r.mx_max_abs_err == 0.0 for r in mx8)
+    if i8 is not None:
+        summary["int8_tops"] = round(min(r.mx_tflops for r in i8), 1)
+        summary["int8_bitwise_ok"] = all(r.mx_max_abs_err == 0.0 for r in i8)
     if sweep is not None:
         summary["cu_sweep"] = f"{sweep.units_seen}/{sweep.units_expected}"
         summary["cu_sweep_ok"] = sweep.ok
@@ -1239,6 +1298,25 @@ def mfma_gemm_mxfp8(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
     _gemm_call("cc_mfma_gemm_mxfp8", "mfma_gemm_mxfp8", device_index, a_ptr,
                sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k, fa,
                fa if fmt_b is None else _fp8_fmt(fmt_b))
+
+
+def mfma_gemm_i8(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
+                 m: int, n: int, k: int, shape="32x32x32") -> None:
+    """INT8 GEMM with exact 32-bit sums: C[M,N] int32 = A[M,K] @ Bt[N,K]^T,
+    A and Bt int8 row-major; ``shape`` "32x32x32" (0) or "16x16x64" (1)
+    picks the integer MFMA. M, N and K multiples of 128, K at most 130944
+    (no sum can leave 32 bits), 16-byte aligned pointers; anything else
+    raises with rc=-2."""
+    _gemm_call("cc_mfma_gemm_i8", "mfma_gemm_i8", device_index, a_ptr, bt_ptr,
+               c_ptr, m, n, k, _i8_shape(shape))
+
+
+def ref_gemm_i8_i32(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
+                    m: int, n: int, k: int) -> None:
+    """VALU reference of :func:`mfma_gemm_i8` (sign-extended bytes, 32-bit
+    multiply and add in k order, no MFMA): any M and N, K at most 130944."""
+    _gemm_call("cc_ref_gemm_i8_i32", "ref_gemm_i8_i32",
+               device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
 
 
 def ref_gemm_mxfp8_f32(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,

@@ -22,11 +22,16 @@
 //                      scales) MFMA GEMM: mfma_gemm_mxfp8_128<FA, FB>,
 //                      LDS DMA with the operand's k permutation folded
 //                      into the source address (swz8mx);
+//   gemm_i8.hip        INT8 MFMA GEMM with exact int32 sums:
+//                      mfma_gemm_i8_128<SHAPE>, the 32x32x32 and the
+//                      16x16x64 integer op, each 32-byte LDS fragment
+//                      split over two MFMAs;
 //   probe_kernels.hip  fills, ref_gemm_f32 (plain VALU fp32 GEMM of the
 //                      same inputs: the independent on-device ground
 //                      truth), the MXFP4 fills and ref_gemm_mxfp4_f32,
 //                      fill_fp6_exact and ref_gemm_mxfp6_f32<FMT>,
 //                      fill_fp8_exact and ref_gemm_mxfp8_f32<FA, FB>,
+//                      fill_i8_lcg, ref_gemm_i8_i32 and max_abs_diff_i32,
 //                      max-diff, checksum, LDS, HBM, liveness;
 //   cu_sweep.hip       compute-unit sweep: cu_sweep (per-SIMD MFMA chains
 //                      and a whole-LDS march, keyed by the hardware ID
@@ -46,7 +51,7 @@
 //                      a DeviceCtx, timed_ms, read_back, DeviceHop;
 //   host_pattern.hip   the CPU fill and compare of the host-link leg
 //                      (plain C++, no HIP call);
-//   probe_legs.hip     the twelve legs and the steps the GEMM legs share.
+//   probe_legs.hip     the thirteen legs and the steps the GEMM legs share.
 //
 // cc_attest_device runs five legs in order:
 //   1. probe_bf16  — production bf16 GEMM dispatch, timed, compared
@@ -66,6 +71,8 @@
 // per call: the MXFP6 GEMM against ref_gemm_mxfp6_f32, bitwise.
 // cc_attest_mxfp8 is the 8-bit one, one format pair (e4m3 or e5m2 for A
 // and for B) per call: the MXFP8 GEMM against ref_gemm_mxfp8_f32, bitwise.
+// cc_attest_int8 is the integer one, one MFMA shape (32x32x32 or 16x16x64)
+// per call: the INT8 GEMM against ref_gemm_i8_i32, bitwise on int32.
 // cc_cu_sweep is another: cu_sweep.hip's matrix-core and whole-LDS
 // self-test on every SIMD of every CU, with the units it reached read
 // from the hardware ID registers.
@@ -92,6 +99,7 @@
 #include "gemm_fp4.hip"
 #include "gemm_fp6.hip"
 #include "gemm_mxfp8.hip"
+#include "gemm_i8.hip"
 #include "probe_kernels.hip"
 #include "cu_sweep.hip"
 #include "hbm_march.hip"
@@ -401,6 +409,56 @@ int cc_attest_mxfp8(int device, int gemm_dim, int fmt_a, int fmt_b,
   CC_CHECK(dev.events());
   CC_CHECK(dev.mx8.acquire(D, fmt_a, fmt_b));
   CC_TRY(probe_mxfp8(dev, rep));
+
+  rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
+  return 0;
+}
+
+// INT8 GEMM on caller-provided device buffers (layout in gemm_i8.hip):
+// int8 A[M,K], Bt[N,K], int32 C[M,N]; shape 0 = the 32x32x32 MFMA, 1 = the
+// 16x16x64 one. M, N and K multiples of 128, K at most 130944, pointers
+// 16-byte aligned; anything else returns -2 without launching.
+int cc_mfma_gemm_i8(int device, const void* A, const void* Bt, void* C, int M,
+                    int N, int K, int shape) {
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  int rc = launch_i8(shape, A, Bt, C, M, N, K);
+  if (rc != 0) return rc;
+  return (int)hipDeviceSynchronize();
+}
+
+// VALU reference of the same convention: any M and N, K at most 130944.
+int cc_ref_gemm_i8_i32(int device, const void* A, const void* Bt, void* C,
+                       int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0 || K > kI8MaxK) return -2;
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  launch_ref_i8(A, Bt, C, M, N, K);
+  return (int)hipDeviceSynchronize();
+}
+
+// The opt-in INT8 probe for one MFMA shape. gemm_dim below 128 rounds up
+// to 128, otherwise down to a multiple of 128; above 130944 it is refused.
+// The report is CcMxReport, unchanged: the caller knows the shape,
+// mx_tflops carries TOP/s and mx_max_abs_err the largest |C - ref|,
+// computed in integers. rep->ok = 1 iff the MFMA result equals the VALU
+// reference bitwise.
+int cc_attest_int8(int device, int gemm_dim, int shape,
+                   struct CcMxReport* rep) {
+  CC_TRY(report_begin(rep, device, [&] {
+    if ((shape == 0 || shape == 1) && gemm_dim <= kI8MaxK) return 0;
+    snprintf(rep->error, sizeof(rep->error),
+             "shape %d is not 0 or 1, or gemm_dim %d above %d", shape,
+             gemm_dim, kI8MaxK);
+    return -2;
+  }));
+
+  const int D = gemm_dim < BK8 ? BK8 : (gemm_dim / BK8) * BK8;
+  rep->mx_m = rep->mx_n = rep->mx_k = D;
+
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  DeviceCtx& dev = device_ctx(device);
+  CC_CHECK(dev.events());
+  CC_CHECK(dev.i8.acquire(D));
+  CC_TRY(probe_int8(dev, shape, rep));
 
   rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
   return 0;

@@ -270,3 +270,31 @@ static void launch_ref_mxfp8(int fa, int fb, const void* A, const void* SA,
                      (const unsigned char*)SA, (const unsigned char*)Bt,
                      (const unsigned char*)SB, (float*)C, M, N, K);
 }
+
+// Largest K of the INT8 GEMM: the largest multiple of 128 with
+// K * 2^14 <= 2^31 - 1 (|a * b| <= 2^14), so no sum can leave 32 bits and
+// the instruction's overflow behaviour never comes into play.
+constexpr int kI8MaxK = 130944;
+
+// Launch the INT8 MFMA GEMM (no sync); shape 0 = the 32x32x32 op, 1 = the
+// 16x16x64 op. -2 for any other shape, M, N or K that does not fit the
+// 128x128x128 tile, K above kI8MaxK or operands that are not 16-byte
+// aligned.
+static int launch_i8(int shape, const void* A, const void* Bt, void* C, int M,
+                     int N, int K) {
+  if (shape != 0 && shape != 1) return -2;
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BK8) return -2;
+  if (K > kI8MaxK) return -2;
+  if ((((uintptr_t)A | (uintptr_t)Bt | (uintptr_t)C) & 15) != 0) return -2;
+  auto kernel = shape == 0 ? mfma_gemm_i8_128<0> : mfma_gemm_i8_128<1>;
+  hipLaunchKernelGGL(kernel, dim3(N / BN, M / BM), dim3(256), 0, 0,
+                     (const char*)A, (const char*)Bt, (int*)C, M, N, K);
+  return 0;
+}
+
+static void launch_ref_i8(const void* A, const void* Bt, void* C, int M, int N,
+                          int K) {
+  dim3 block(16, 16), grid((N + 15) / 16, (M + 15) / 16);
+  hipLaunchKernelGGL(ref_gemm_i8_i32, grid, block, 0, 0, (const signed char*)A,
+                     (const signed char*)Bt, (int*)C, M, N, K);
+}

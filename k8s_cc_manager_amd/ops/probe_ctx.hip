@@ -184,6 +184,33 @@ struct Mx8Ctx {
   }
 };
 
+// The INT8 leg (cc_attest_int8), same rules as MainCtx, keyed by dim
+// alone: both MFMA shapes read the same fill, so they share the cached
+// reference.
+struct I8Ctx {
+  int dim = 0;
+  int ref_valid = 0;
+  DevBuf<signed char> dA, dB;  // one byte per element
+  DevBuf<int> dC, dRef;
+  DevBuf<unsigned> dErr;  // max |C - ref|, an integer
+  DevBuf<unsigned long long> dSum;
+
+  hipError_t acquire(int D) {
+    if (dim == D) return hipSuccess;
+    *this = I8Ctx{};
+    const size_t n = (size_t)D * D;
+    hipError_t e;
+    if ((e = dA.ensure(n)) || (e = dB.ensure(n)) ||
+        (e = dC.ensure(n * sizeof(int))) ||
+        (e = dRef.ensure(n * sizeof(int))) ||
+        (e = dErr.ensure(sizeof(unsigned))) ||
+        (e = dSum.ensure(sizeof(unsigned long long))))
+      return e;
+    dim = D;
+    return hipSuccess;
+  }
+};
+
 // The compute-unit sweep (cc_cu_sweep): fixed sizes, allocated once.
 struct SweepCtx {
   DevBuf<unsigned> dSweepTab;
@@ -229,6 +256,7 @@ struct DeviceCtx {
   MxCtx mx;
   Mx6Ctx mx6;
   Mx8Ctx mx8;
+  I8Ctx i8;
   SweepCtx sweep;
   HbmCtx hbm;
   HostCtx host;

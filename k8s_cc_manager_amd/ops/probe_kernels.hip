@@ -291,6 +291,67 @@ __global__ void ref_gemm_mxfp8_f32(const unsigned char* __restrict__ A,
   C[(long)row * N + col] = acc;
 }
 
+// ---------------------------------------------------------------------------
+// INT8 leg: fill, the VALU reference and the integer compare (data
+// convention in gemm_i8.hip).
+// ---------------------------------------------------------------------------
+// n signed bytes over the full range -128..127: integer sums are exact
+// for any data in any order, so there is no magnitude budget to keep.
+// The LCG's byte is uniform: -128 occurs in both seeded fills at every
+// gate dim (about n / 256 times).
+__global__ void fill_i8_lcg(signed char* __restrict__ out, long n,
+                            uint32_t seed) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    uint32_t x = (uint32_t)i * 1103515245u + seed * 747796405u + 12345u;
+    x ^= x >> 16;
+    x *= 2654435769u;
+    out[i] = (signed char)(unsigned char)(x >> 13);
+  }
+}
+
+// VALU int8 reference GEMM: one thread per C element, sign-extended
+// bytes, 32-bit multiply and add in k order. No MFMA, no dot instruction
+// asked for. K * 2^14 <= 2^31 - 1 is the caller's to keep.
+__global__ void ref_gemm_i8_i32(const signed char* __restrict__ A,
+                                const signed char* __restrict__ Bt,
+                                int* __restrict__ C, int M, int N, int K) {
+  int col = blockIdx.x * blockDim.x + threadIdx.x;
+  int row = blockIdx.y * blockDim.y + threadIdx.y;
+  if (row >= M || col >= N) return;
+  const signed char* a = A + (long)row * K;
+  const signed char* b = Bt + (long)col * K;
+  int acc = 0;
+  for (int k = 0; k < K; ++k) acc += (int)a[k] * (int)b[k];
+  C[(long)row * N + col] = acc;
+}
+
+// max |x-y| over n int32 elements -> out[0] (pre-zeroed), the difference
+// taken in 64 bits. max_abs_diff subtracts floats and cannot be used on
+// reinterpreted integers.
+__global__ void max_abs_diff_i32(const int* __restrict__ x,
+                                 const int* __restrict__ y, long n,
+                                 unsigned* out) {
+  __shared__ unsigned smax[256];
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+  unsigned m = 0;
+  for (; i < n; i += stride) {
+    long d = (long)x[i] - (long)y[i];
+    unsigned a = (unsigned)(d < 0 ? -d : d);  // at most 2^32 - 1
+    m = a > m ? a : m;
+  }
+  smax[threadIdx.x] = m;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s && smax[threadIdx.x + s] > smax[threadIdx.x])
+      smax[threadIdx.x] = smax[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) atomicMax(out, smax[0]);
+}
+
 // max |x-y| reduction over n elements -> out[0] (pre-zeroed)
 __global__ void max_abs_diff(const float* __restrict__ x,
                              const float* __restrict__ y, long n,

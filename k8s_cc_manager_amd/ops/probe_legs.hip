@@ -322,6 +322,45 @@ static int probe_mxfp8(DeviceCtx& dev, CcMxReport* rep) {
                            dSum, &rep->mx_checksum);
 }
 
+// INT8 leg: the full byte range -128..127 through the integer MFMA of
+// `shape` (0 = 32x32x32, 1 = 16x16x64), bitwise against the VALU
+// reference, which both shapes share. mx_tflops carries TOP/s and
+// mx_max_abs_err max |C - ref| computed in integers: 0.0 iff every
+// element agrees bitwise.
+static int probe_int8(DeviceCtx& dev, int shape, CcMxReport* rep) {
+  I8Ctx& ctx = dev.i8;
+  const int D = ctx.dim;
+  const long elems = (long)D * D;
+  signed char *dA = ctx.dA, *dB = ctx.dB;
+  int *dC = ctx.dC, *dRef = ctx.dRef;
+  unsigned* dErr = ctx.dErr;
+  unsigned long long* dSum = ctx.dSum;
+  CC_CHECK(hipMemset(dErr, 0, sizeof(unsigned)));
+  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
+  // 0x7f7f7f7f: no sum can reach it while K < 130560, so an output the
+  // kernel never wrote shows as a difference
+  CC_CHECK(hipMemset(dC, 0x7F, elems * sizeof(int)));
+
+  hipLaunchKernelGGL(fill_i8_lcg, dim3(2048), dim3(256), 0, 0, dA, elems, 1u);
+  hipLaunchKernelGGL(fill_i8_lcg, dim3(2048), dim3(256), 0, 0, dB, elems, 7u);
+
+  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops,
+                    [&] { return launch_i8(shape, dA, dB, dC, D, D, D); }));
+  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms,
+                          [&] { launch_ref_i8(dA, dB, dRef, D, D, D); }));
+  hipLaunchKernelGGL(max_abs_diff_i32, dim3(1024), dim3(256), 0, 0, dC, dRef,
+                     elems, dErr);
+  // the checksum hashes bit patterns, so it takes the int32 bits as they are
+  hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0,
+                     (const float*)dC, elems, dSum);
+  CC_CHECK(hipDeviceSynchronize());
+  unsigned err = 0;
+  CC_CHECK(read_back(dErr, &err));
+  CC_CHECK(read_back(dSum, &rep->mx_checksum));
+  rep->mx_max_abs_err = (float)err;
+  return 0;
+}
+
 // The golden C images for `rounds`, a constant: computed once per
 // (device, rounds). *ms = 0.0 when the cached images were used. `rep`
 // is whatever holds the error text (a report, or ErrorText).
