@@ -437,6 +437,9 @@ _BINDINGS = {
     "cc_mfma_gemm_i8": (_INT, _GEMM + [_INT]),
     "cc_ref_gemm_i8_i32": (_INT, _GEMM),
     "cc_attest_int8": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CMxReport)]),
+    "cc_mfma_gemm_f64": (_INT, _GEMM),
+    "cc_ref_gemm_f64": (_INT, _GEMM),
+    "cc_attest_fp64": (_INT, [_INT, _INT, ctypes.POINTER(_CMxReport)]),
     "cc_mx_report_sizeof": (_INT, []),
     "cc_cu_sweep": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CSweepReport)]),
     "cc_cu_sweep_gold": (_INT, [_INT, _INT, ctypes.POINTER(ctypes.c_float)]),
@@ -712,6 +715,38 @@ def attest_int8(device_index: int, gemm_dim: int = 1024,
         "bitwise ok",
         rep.device,
         code,
+        rep.mx_tflops,
+        rep.mx_dim,
+        rep.mx_dim,
+        rep.mx_dim,
+    )
+    return rep
+
+
+def attest_fp64(device_index: int, gemm_dim: int = 1024) -> MxReport:
+    """Run the FP64 probe on one GPU: the fp64 MFMA GEMM on integer-valued
+    doubles up to 2^20 - 1 against the VALU fma reference. Every sum is
+    exact, so the two must be equal. The report is MxReport:
+    ``mx_max_abs_err`` carries the largest |C - ref|, taken in double (a
+    NaN counts as infinity). Raises on failure. gemm_dim below 128 rounds
+    up to 128, otherwise down to a multiple; above 8192 (K * 2^40 must
+    stay within 2^53) the library refuses it with rc=-2."""
+    lib = _load()
+    c = _CMxReport()
+    rc = lib.cc_attest_fp64(device_index, gemm_dim, ctypes.byref(c))
+    rep = MxReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"device {device_index}: fp64 probe runtime error rc={rc}: {rep.error}"
+        )
+    if not rep.ok:
+        raise AttestationError(
+            f"device {device_index}: fp64 attestation FAILED "
+            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
+        )
+    logger.info(
+        "attested device %d: fp64 GEMM %.1f TF/s (%dx%dx%d), exact",
+        rep.device,
         rep.mx_tflops,
         rep.mx_dim,
         rep.mx_dim,
@@ -1124,6 +1159,9 @@ def attest_device_by_bdf(device) -> dict:
     i8 = None
     if os.environ.get("CC_ATTEST_INT8", "0") == "1":
         i8 = [attest_int8(idx, gemm_dim=gemm_dim, shape=s) for s in INT8_SHAPES]
+    f64 = None
+    if os.environ.get("CC_ATTEST_FP64", "0") == "1":
+        f64 = attest_fp64(idx, gemm_dim=gemm_dim)
     sweep = None
     if os.environ.get("CC_ATTEST_CU_SWEEP", "0") == "1":
         sweep = sweep_compute_units(idx)
@@ -1172,6 +1210,9 @@ def attest_device_by_bdf(device) -> dict:
     if i8 is not None:
         summary["int8_tops"] = round(min(r.mx_tflops for r in i8), 1)
         summary["int8_bitwise_ok"] = all(r.mx_max_abs_err == 0.0 for r in i8)
+    if f64 is not None:
+        summary["fp64_tflops"] = round(f64.mx_tflops, 1)
+        summary["fp64_exact_ok"] = f64.mx_max_abs_err == 0.0
     if sweep is not None:
         summary["cu_sweep"] = f"{sweep.units_seen}/{sweep.units_expected}"
         summary["cu_sweep_ok"] = sweep.ok
@@ -1316,6 +1357,23 @@ def ref_gemm_i8_i32(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
     """VALU reference of :func:`mfma_gemm_i8` (sign-extended bytes, 32-bit
     multiply and add in k order, no MFMA): any M and N, K at most 130944."""
     _gemm_call("cc_ref_gemm_i8_i32", "ref_gemm_i8_i32",
+               device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
+
+
+def mfma_gemm_f64(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
+                  m: int, n: int, k: int) -> None:
+    """FP64 GEMM on the double-precision matrix core: C[M,N] = A[M,K] @
+    Bt[N,K]^T, all float64 row-major. M and N multiples of 128, K of 16,
+    16-byte aligned pointers; anything else raises with rc=-2."""
+    _gemm_call("cc_mfma_gemm_f64", "mfma_gemm_f64",
+               device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
+
+
+def ref_gemm_f64(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
+                 m: int, n: int, k: int) -> None:
+    """VALU reference of :func:`mfma_gemm_f64` (fma in double, k order, no
+    MFMA): any M, N and K above 0."""
+    _gemm_call("cc_ref_gemm_f64", "ref_gemm_f64",
                device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
 
 

@@ -26,12 +26,16 @@
 //                      mfma_gemm_i8_128<SHAPE>, the 32x32x32 and the
 //                      16x16x64 integer op, each 32-byte LDS fragment
 //                      split over two MFMAs;
-//   probe_kernels.hip  fills, ref_gemm_f32 (plain VALU fp32 GEMM of the
+//   gemm_f64.hip       FP64 MFMA GEMM: mfma_gemm_f64_128, the 16x16x4 f64
+//                      op, eight waves of 32x64, the int8 LDS image read
+//                      as four doubles per lane, an fp64 C/D epilogue;
+//   probe_kernels.hip fills, ref_gemm_f32 (plain VALU fp32 GEMM of the
 //                      same inputs: the independent on-device ground
 //                      truth), the MXFP4 fills and ref_gemm_mxfp4_f32,
 //                      fill_fp6_exact and ref_gemm_mxfp6_f32<FMT>,
 //                      fill_fp8_exact and ref_gemm_mxfp8_f32<FA, FB>,
 //                      fill_i8_lcg, ref_gemm_i8_i32 and max_abs_diff_i32,
+//                      fill_f64_exact, ref_gemm_f64 and max_abs_diff_f64,
 //                      max-diff, checksum, LDS, HBM, liveness;
 //   cu_sweep.hip       compute-unit sweep: cu_sweep (per-SIMD MFMA chains
 //                      and a whole-LDS march, keyed by the hardware ID
@@ -51,7 +55,7 @@
 //                      a DeviceCtx, timed_ms, read_back, DeviceHop;
 //   host_pattern.hip   the CPU fill and compare of the host-link leg
 //                      (plain C++, no HIP call);
-//   probe_legs.hip     the thirteen legs and the steps the GEMM legs share.
+//   probe_legs.hip     the fourteen legs and the steps the GEMM legs share.
 //
 // cc_attest_device runs five legs in order:
 //   1. probe_bf16  — production bf16 GEMM dispatch, timed, compared
@@ -73,6 +77,8 @@
 // and for B) per call: the MXFP8 GEMM against ref_gemm_mxfp8_f32, bitwise.
 // cc_attest_int8 is the integer one, one MFMA shape (32x32x32 or 16x16x64)
 // per call: the INT8 GEMM against ref_gemm_i8_i32, bitwise on int32.
+// cc_attest_fp64 is the double-precision one: the FP64 MFMA GEMM against
+// ref_gemm_f64 (v_fma_f64) on data whose every sum is exact, by value.
 // cc_cu_sweep is another: cu_sweep.hip's matrix-core and whole-LDS
 // self-test on every SIMD of every CU, with the units it reached read
 // from the hardware ID registers.
@@ -100,6 +106,7 @@
 #include "gemm_fp6.hip"
 #include "gemm_mxfp8.hip"
 #include "gemm_i8.hip"
+#include "gemm_f64.hip"
 #include "probe_kernels.hip"
 #include "cu_sweep.hip"
 #include "hbm_march.hip"
@@ -459,6 +466,54 @@ int cc_attest_int8(int device, int gemm_dim, int shape,
   CC_CHECK(dev.events());
   CC_CHECK(dev.i8.acquire(D));
   CC_TRY(probe_int8(dev, shape, rep));
+
+  rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
+  return 0;
+}
+
+// FP64 GEMM on caller-provided device buffers (layout in gemm_f64.hip):
+// fp64 A[M,K], Bt[N,K], C[M,N]. M and N multiples of 128, K a multiple of
+// 16, pointers 16-byte aligned; anything else returns -2 without launching.
+int cc_mfma_gemm_f64(int device, const void* A, const void* Bt, void* C, int M,
+                     int N, int K) {
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  int rc = launch_f64(A, Bt, C, M, N, K);
+  if (rc != 0) return rc;
+  return (int)hipDeviceSynchronize();
+}
+
+// VALU reference of the same convention (fma in double, k order): any M,
+// N and K above 0.
+int cc_ref_gemm_f64(int device, const void* A, const void* Bt, void* C, int M,
+                    int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return -2;
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  launch_ref_f64(A, Bt, C, M, N, K);
+  return (int)hipDeviceSynchronize();
+}
+
+// The opt-in FP64 probe. gemm_dim below 128 rounds up to 128, otherwise
+// down to a multiple of 128; above kF64ExactDim it is refused, because
+// the leg's sums would no longer be exact. The report is CcMxReport,
+// unchanged: mx_max_abs_err carries the largest |C - ref|, taken in
+// double. rep->ok = 1 iff the MFMA result equals the VALU reference.
+int cc_attest_fp64(int device, int gemm_dim, struct CcMxReport* rep) {
+  CC_TRY(report_begin(rep, device, [&] {
+    if (gemm_dim <= kF64ExactDim) return 0;
+    snprintf(rep->error, sizeof(rep->error),
+             "gemm_dim %d above %d: the fp64 leg's sums would not be exact",
+             gemm_dim, kF64ExactDim);
+    return -2;
+  }));
+
+  const int D = gemm_dim < BM ? BM : (gemm_dim / BM) * BM;
+  rep->mx_m = rep->mx_n = rep->mx_k = D;
+
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  DeviceCtx& dev = device_ctx(device);
+  CC_CHECK(dev.events());
+  CC_CHECK(dev.f64.acquire(D));
+  CC_TRY(probe_fp64(dev, rep));
 
   rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
   return 0;

@@ -298,3 +298,27 @@ static void launch_ref_i8(const void* A, const void* Bt, void* C, int M, int N,
   hipLaunchKernelGGL(ref_gemm_i8_i32, grid, block, 0, 0, (const signed char*)A,
                      (const signed char*)Bt, (int*)C, M, N, K);
 }
+
+// Launch the FP64 MFMA GEMM (no sync). -2 for M or N that is no multiple
+// of the 128 tile, K that is no multiple of the 16-double K-tile, or
+// operands that are not 16-byte aligned. No K cap here: the GEMM rounds
+// like any fp64 sum; the exactness cap belongs to the leg (kF64ExactDim).
+static int launch_f64(const void* A, const void* Bt, void* C, int M, int N,
+                      int K) {
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BK64) return -2;
+  if ((((uintptr_t)A | (uintptr_t)Bt | (uintptr_t)C) & 15) != 0) return -2;
+  hipLaunchKernelGGL(mfma_gemm_f64_128, dim3(N / BN, M / BM), dim3(512), 0, 0,
+                     (const double*)A, (const double*)Bt, (double*)C, M, N, K);
+  return 0;
+}
+
+static void launch_ref_f64(const void* A, const void* Bt, void* C, int M,
+                           int N, int K) {
+  dim3 block(16, 16), grid((N + 15) / 16, (M + 15) / 16);
+  hipLaunchKernelGGL(ref_gemm_f64, grid, block, 0, 0, (const double*)A,
+                     (const double*)Bt, (double*)C, M, N, K);
+}
+
+// Largest dim of the FP64 leg: the fill's products are integers below 2^40,
+// so while K * 2^40 <= 2^53 every partial sum is exact in any order.
+constexpr int kF64ExactDim = 8192;

@@ -211,6 +211,30 @@ struct I8Ctx {
   }
 };
 
+// The FP64 leg (cc_attest_fp64), same rules as MainCtx, keyed by dim.
+// 32 bytes per output element (A, B, C and the reference, 8 each): 32 MiB
+// at dim 1024, 2 GiB at the leg's cap of 8192.
+struct F64Ctx {
+  int dim = 0;
+  int ref_valid = 0;
+  DevBuf<double> dA, dB, dC, dRef;
+  DevBuf<float> dErr;  // max |C - ref|, reduced in double
+  DevBuf<unsigned long long> dSum;
+
+  hipError_t acquire(int D) {
+    if (dim == D) return hipSuccess;
+    *this = F64Ctx{};
+    const size_t n = (size_t)D * D * sizeof(double);
+    hipError_t e;
+    if ((e = dA.ensure(n)) || (e = dB.ensure(n)) || (e = dC.ensure(n)) ||
+        (e = dRef.ensure(n)) || (e = dErr.ensure(sizeof(float))) ||
+        (e = dSum.ensure(sizeof(unsigned long long))))
+      return e;
+    dim = D;
+    return hipSuccess;
+  }
+};
+
 // The compute-unit sweep (cc_cu_sweep): fixed sizes, allocated once.
 struct SweepCtx {
   DevBuf<unsigned> dSweepTab;
@@ -257,6 +281,7 @@ struct DeviceCtx {
   Mx6Ctx mx6;
   Mx8Ctx mx8;
   I8Ctx i8;
+  F64Ctx f64;
   SweepCtx sweep;
   HbmCtx hbm;
   HostCtx host;

@@ -352,6 +352,76 @@ __global__ void max_abs_diff_i32(const int* __restrict__ x,
   if (threadIdx.x == 0) atomicMax(out, smax[0]);
 }
 
+// ---------------------------------------------------------------------------
+// FP64 leg: fill, the VALU reference and the double compare (data
+// convention in gemm_f64.hip).
+// ---------------------------------------------------------------------------
+// n integer-valued doubles with |v| <= 2^20 - 1: the hash's top 20 bits
+// are the magnitude (the whole range, odd values included), bit 11 the
+// sign. A product is an integer below 2^40 (beyond fp32's 24 bits), and
+// while K * 2^40 <= 2^53 (K <= 8192) every partial sum in any order is an
+// integer below 2^53: exact in fp64.
+__global__ void fill_f64_exact(double* __restrict__ out, long n,
+                               uint32_t seed) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    uint32_t x = (uint32_t)i * 1103515245u + seed * 747796405u + 12345u;
+    x ^= x >> 16;
+    x *= 2654435769u;
+    const double mag = (double)(x >> 12);
+    out[i] = (x & 0x800u) ? -mag : mag;
+  }
+}
+
+// VALU fp64 reference GEMM: one thread per C element, fma in double in k
+// order (v_fmac_f64 in the shipped code). No MFMA: the VALU's fp64 FMA is
+// a different datapath from the matrix core.
+__global__ void ref_gemm_f64(const double* __restrict__ A,
+                             const double* __restrict__ Bt,
+                             double* __restrict__ C, int M, int N, int K) {
+  int col = blockIdx.x * blockDim.x + threadIdx.x;
+  int row = blockIdx.y * blockDim.y + threadIdx.y;
+  if (row >= M || col >= N) return;
+  const double* a = A + (long)row * K;
+  const double* b = Bt + (long)col * K;
+  double acc = 0.0;
+  for (int k = 0; k < K; ++k) acc = fma(a[k], b[k], acc);
+  C[(long)row * N + col] = acc;
+}
+
+// max |x-y| over n doubles -> out[0] (pre-zeroed), for the report's float
+// field. The difference and the reduction are in double and compare by
+// value (+0 equals -0); a NaN on either side counts as infinity. The
+// conversion to float clamps any nonzero difference up to the smallest
+// normal float, so that it can neither round nor be flushed to 0.0f.
+__global__ void max_abs_diff_f64(const double* __restrict__ x,
+                                 const double* __restrict__ y, long n,
+                                 float* out) {
+  __shared__ double smax[256];
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+  double m = 0.0;
+  for (; i < n; i += stride) {
+    double d = fabs(x[i] - y[i]);
+    if (!(d == d)) d = __builtin_huge_val();
+    m = d > m ? d : m;
+  }
+  smax[threadIdx.x] = m;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (threadIdx.x < s && smax[threadIdx.x + s] > smax[threadIdx.x])
+      smax[threadIdx.x] = smax[threadIdx.x + s];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0 && smax[0] > 0.0) {
+    float f = (float)smax[0];
+    if (!(f >= 1.17549435e-38f)) f = 1.17549435e-38f;
+    // fp32 max via atomicMax on the bit pattern (values are > 0)
+    atomicMax((unsigned int*)out, __float_as_uint(f));
+  }
+}
+
 // max |x-y| reduction over n elements -> out[0] (pre-zeroed)
 __global__ void max_abs_diff(const float* __restrict__ x,
                              const float* __restrict__ y, long n,

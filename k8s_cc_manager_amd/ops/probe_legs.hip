@@ -361,6 +361,44 @@ static int probe_int8(DeviceCtx& dev, int shape, CcMxReport* rep) {
   return 0;
 }
 
+// FP64 leg: integer-valued doubles up to 2^20 - 1 through the fp64 MFMA,
+// against the VALU fma reference. Every sum is exact while D <=
+// kF64ExactDim (fill_f64_exact), so the two must be equal:
+// mx_max_abs_err is max |C - ref| taken in double, 0.0 iff every element
+// agrees by value. The compare and the checksum are the leg's own
+// launches, as in probe_int8: compare_read_back is typed for fp32.
+static int probe_fp64(DeviceCtx& dev, CcMxReport* rep) {
+  F64Ctx& ctx = dev.f64;
+  const int D = ctx.dim;
+  const long elems = (long)D * D;
+  double *dA = ctx.dA, *dB = ctx.dB, *dC = ctx.dC, *dRef = ctx.dRef;
+  float* dErr = ctx.dErr;
+  unsigned long long* dSum = ctx.dSum;
+  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
+  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
+  // all ones is a NaN: an output the kernel never wrote is a mismatch
+  CC_CHECK(hipMemset(dC, 0xFF, elems * sizeof(double)));
+
+  hipLaunchKernelGGL(fill_f64_exact, dim3(2048), dim3(256), 0, 0, dA, elems,
+                     1u);
+  hipLaunchKernelGGL(fill_f64_exact, dim3(2048), dim3(256), 0, 0, dB, elems,
+                     7u);
+
+  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops,
+                    [&] { return launch_f64(dA, dB, dC, D, D, D); }));
+  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms,
+                          [&] { launch_ref_f64(dA, dB, dRef, D, D, D); }));
+  hipLaunchKernelGGL(max_abs_diff_f64, dim3(1024), dim3(256), 0, 0, dC, dRef,
+                     elems, dErr);
+  // the checksum hashes bit patterns: each double as its two 32-bit halves
+  hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0,
+                     (const float*)dC, 2 * elems, dSum);
+  CC_CHECK(hipDeviceSynchronize());
+  CC_CHECK(read_back(dErr, &rep->mx_max_abs_err));
+  CC_CHECK(read_back(dSum, &rep->mx_checksum));
+  return 0;
+}
+
 // The golden C images for `rounds`, a constant: computed once per
 // (device, rounds). *ms = 0.0 when the cached images were used. `rep`
 // is whatever holds the error text (a report, or ErrorText).
