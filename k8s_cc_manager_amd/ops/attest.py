@@ -440,6 +440,10 @@ _BINDINGS = {
     "cc_mfma_gemm_f64": (_INT, _GEMM),
     "cc_ref_gemm_f64": (_INT, _GEMM),
     "cc_attest_fp64": (_INT, [_INT, _INT, ctypes.POINTER(_CMxReport)]),
+    # device, Ac, Am, Bt, C, M, N, K [, shape]
+    "cc_mfma_gemm_sp24": (_INT, [_INT] + [_PTR] * 4 + [_INT] * 4),
+    "cc_ref_gemm_sp24_f32": (_INT, [_INT] + [_PTR] * 4 + [_INT] * 3),
+    "cc_attest_sparse": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CMxReport)]),
     "cc_mx_report_sizeof": (_INT, []),
     "cc_cu_sweep": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CSweepReport)]),
     "cc_cu_sweep_gold": (_INT, [_INT, _INT, ctypes.POINTER(ctypes.c_float)]),
@@ -747,6 +751,79 @@ def attest_fp64(device_index: int, gemm_dim: int = 1024) -> MxReport:
     logger.info(
         "attested device %d: fp64 GEMM %.1f TF/s (%dx%dx%d), exact",
         rep.device,
+        rep.mx_tflops,
+        rep.mx_dim,
+        rep.mx_dim,
+        rep.mx_dim,
+    )
+    return rep
+
+
+# the bf16 SMFMAC shapes of the sparse leg by name, numbered as INT8_SHAPES
+SPARSE_SHAPES = {"32x32x32": 0, "16x16x64": 1}
+
+# the six legal 2:4 index nibbles, pos0 in bits 1:0 below pos1 in bits 3:2:
+# (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
+SP24_NIBBLES = (0x4, 0x8, 0xC, 0x9, 0xD, 0xE)
+
+
+def _sparse_shape(shape) -> int:
+    """"32x32x32" / "16x16x64" or a number; a number goes to the library
+    as it is, which refuses anything but 0 and 1 with -2."""
+    if isinstance(shape, str):
+        if shape not in SPARSE_SHAPES:
+            raise AttestationError(f"unknown sparse MFMA shape {shape!r}")
+        return SPARSE_SHAPES[shape]
+    return int(shape)
+
+
+def sp24_dense(ac, am):
+    """The host model of the 2:4 convention (docs/KERNELS.md, "Sparse
+    leg"): scatter the kept values ``ac[M, K/2]`` to dense ``[M, K]`` by
+    the index bytes ``am[M, K/8]`` (uint8). Byte b holds group 2b in its
+    low nibble and group 2b+1 in its high one; in a nibble, bits 1:0 are
+    the position of the group's first kept value and bits 3:2 that of its
+    second. Nibbles are decoded literally. CPU or GPU torch tensors; the
+    result has ``ac``'s dtype and device."""
+    import torch
+
+    m, groups = ac.shape[0], ac.shape[1] // 2
+    byte = am.to(torch.int64)
+    nib = torch.stack((byte & 15, byte >> 4), dim=2).reshape(m, groups)
+    pos = torch.stack((nib & 3, nib >> 2), dim=2)  # [M, K/4, 2]
+    dense = ac.new_zeros(m, groups, 4)
+    dense.scatter_(2, pos, ac.reshape(m, groups, 2))
+    return dense.reshape(m, 4 * groups)
+
+
+def attest_sparse(device_index: int, gemm_dim: int = 1024,
+                  shape="32x32x32") -> MxReport:
+    """Run the sparse probe on one GPU for one bf16 SMFMAC shape
+    ("32x32x32" / "16x16x64" or 0 / 1): the 2:4 structured-sparse GEMM on
+    exactly summable values and all six legal index nibbles against the
+    VALU reference, bitwise. The report is MxReport: ``mx_tflops`` is the
+    dense-equivalent rate, 2 * dim^3 over the time (the sparse core
+    performs half those multiplies). Raises on failure. gemm_dim below 128
+    rounds up to 128, otherwise down to a multiple."""
+    lib = _load()
+    c = _CMxReport()
+    code = _sparse_shape(shape)
+    rc = lib.cc_attest_sparse(device_index, gemm_dim, code, ctypes.byref(c))
+    rep = MxReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"device {device_index}: sparse probe runtime error rc={rc}: {rep.error}"
+        )
+    if not rep.ok:
+        raise AttestationError(
+            f"device {device_index}: sparse shape {code} attestation FAILED "
+            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
+        )
+    logger.info(
+        "attested device %d: 2:4 sparse bf16 shape %d GEMM %.1f TF/s "
+        "dense-equivalent (%dx%dx%d), bitwise ok",
+        rep.device,
+        code,
         rep.mx_tflops,
         rep.mx_dim,
         rep.mx_dim,
@@ -1162,6 +1239,10 @@ def attest_device_by_bdf(device) -> dict:
     f64 = None
     if os.environ.get("CC_ATTEST_FP64", "0") == "1":
         f64 = attest_fp64(idx, gemm_dim=gemm_dim)
+    sp = None
+    if os.environ.get("CC_ATTEST_SPARSE", "0") == "1":
+        sp = [attest_sparse(idx, gemm_dim=gemm_dim, shape=s)
+              for s in SPARSE_SHAPES]
     sweep = None
     if os.environ.get("CC_ATTEST_CU_SWEEP", "0") == "1":
         sweep = sweep_compute_units(idx)
@@ -1213,6 +1294,9 @@ def attest_device_by_bdf(device) -> dict:
     if f64 is not None:
         summary["fp64_tflops"] = round(f64.mx_tflops, 1)
         summary["fp64_exact_ok"] = f64.mx_max_abs_err == 0.0
+    if sp is not None:
+        summary["sparse_tflops"] = round(min(r.mx_tflops for r in sp), 1)
+        summary["sparse_bitwise_ok"] = all(r.mx_max_abs_err == 0.0 for r in sp)
     if sweep is not None:
         summary["cu_sweep"] = f"{sweep.units_seen}/{sweep.units_expected}"
         summary["cu_sweep_ok"] = sweep.ok
@@ -1375,6 +1459,27 @@ def ref_gemm_f64(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
     MFMA): any M, N and K above 0."""
     _gemm_call("cc_ref_gemm_f64", "ref_gemm_f64",
                device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
+
+
+def mfma_gemm_sp24(device_index: int, ac_ptr: int, am_ptr: int, bt_ptr: int,
+                   c_ptr: int, m: int, n: int, k: int,
+                   shape="32x32x32") -> None:
+    """2:4 structured-sparse bf16 GEMM on the sparse matrix core: C[M,N]
+    fp32 = sp24_dense(Ac, Am) @ Bt[N,K]^T, with Ac[M,K/2] bf16 the kept
+    values, Am[M,K/8] uint8 their positions (see :func:`sp24_dense`) and Bt
+    bf16 dense, all row-major; ``k`` is the dense K. ``shape`` "32x32x32"
+    (0) or "16x16x64" (1) picks the SMFMAC. M, N and K multiples of 128,
+    16-byte aligned pointers; anything else raises with rc=-2."""
+    _gemm_call("cc_mfma_gemm_sp24", "mfma_gemm_sp24", device_index, ac_ptr,
+               am_ptr, bt_ptr, c_ptr, m, n, k, _sparse_shape(shape))
+
+
+def ref_gemm_sp24_f32(device_index: int, ac_ptr: int, am_ptr: int, bt_ptr: int,
+                      c_ptr: int, m: int, n: int, k: int) -> None:
+    """VALU reference of :func:`mfma_gemm_sp24` (integer nibble decode, fp32
+    multiply and add in k order, no MFMA): any M and N, K a multiple of 8."""
+    _gemm_call("cc_ref_gemm_sp24_f32", "ref_gemm_sp24_f32", device_index,
+               ac_ptr, am_ptr, bt_ptr, c_ptr, m, n, k)
 
 
 def ref_gemm_mxfp8_f32(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,

@@ -29,6 +29,10 @@
 //   gemm_f64.hip       FP64 MFMA GEMM: mfma_gemm_f64_128, the 16x16x4 f64
 //                      op, eight waves of 32x64, the int8 LDS image read
 //                      as four doubles per lane, an fp64 C/D epilogue;
+//   gemm_sp24.hip      2:4 sparse bf16 GEMM on the SMFMAC ops:
+//                      mfma_gemm_sp24_128<SHAPE>, compressed A and two
+//                      dense B images in LDS, the index straight from
+//                      global into the lane that uses it;
 //   probe_kernels.hip fills, ref_gemm_f32 (plain VALU fp32 GEMM of the
 //                      same inputs: the independent on-device ground
 //                      truth), the MXFP4 fills and ref_gemm_mxfp4_f32,
@@ -36,6 +40,7 @@
 //                      fill_fp8_exact and ref_gemm_mxfp8_f32<FA, FB>,
 //                      fill_i8_lcg, ref_gemm_i8_i32 and max_abs_diff_i32,
 //                      fill_f64_exact, ref_gemm_f64 and max_abs_diff_f64,
+//                      fill_sp24_exact and ref_gemm_sp24_f32,
 //                      max-diff, checksum, LDS, HBM, liveness;
 //   cu_sweep.hip       compute-unit sweep: cu_sweep (per-SIMD MFMA chains
 //                      and a whole-LDS march, keyed by the hardware ID
@@ -55,7 +60,7 @@
 //                      a DeviceCtx, timed_ms, read_back, DeviceHop;
 //   host_pattern.hip   the CPU fill and compare of the host-link leg
 //                      (plain C++, no HIP call);
-//   probe_legs.hip     the fourteen legs and the steps the GEMM legs share.
+//   probe_legs.hip     the fifteen legs and the steps the GEMM legs share.
 //
 // cc_attest_device runs five legs in order:
 //   1. probe_bf16  — production bf16 GEMM dispatch, timed, compared
@@ -79,6 +84,8 @@
 // per call: the INT8 GEMM against ref_gemm_i8_i32, bitwise on int32.
 // cc_attest_fp64 is the double-precision one: the FP64 MFMA GEMM against
 // ref_gemm_f64 (v_fma_f64) on data whose every sum is exact, by value.
+// cc_attest_sparse is the structured-sparsity one, one SMFMAC shape per
+// call: the 2:4 sparse bf16 GEMM against ref_gemm_sp24_f32, bitwise.
 // cc_cu_sweep is another: cu_sweep.hip's matrix-core and whole-LDS
 // self-test on every SIMD of every CU, with the units it reached read
 // from the hardware ID registers.
@@ -107,6 +114,7 @@
 #include "gemm_mxfp8.hip"
 #include "gemm_i8.hip"
 #include "gemm_f64.hip"
+#include "gemm_sp24.hip"
 #include "probe_kernels.hip"
 #include "cu_sweep.hip"
 #include "hbm_march.hip"
@@ -514,6 +522,56 @@ int cc_attest_fp64(int device, int gemm_dim, struct CcMxReport* rep) {
   CC_CHECK(dev.events());
   CC_CHECK(dev.f64.acquire(D));
   CC_TRY(probe_fp64(dev, rep));
+
+  rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
+  return 0;
+}
+
+// 2:4 sparse bf16 GEMM on caller-provided device buffers (convention in
+// gemm_sp24.hip): bf16 Ac[M,K/2], uint8 Am[M,K/8], bf16 Bt[N,K], fp32
+// C[M,N]; K is the dense K; shape 0 = the 32x32x32 SMFMAC, 1 = the
+// 16x16x64 one. M, N and K multiples of 128, pointers 16-byte aligned;
+// anything else returns -2 without launching.
+int cc_mfma_gemm_sp24(int device, const void* Ac, const void* Am,
+                      const void* Bt, void* C, int M, int N, int K,
+                      int shape) {
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  int rc = launch_sp24(shape, Ac, Am, Bt, C, M, N, K);
+  if (rc != 0) return rc;
+  return (int)hipDeviceSynchronize();
+}
+
+// VALU reference of the same convention: any M and N, K a multiple of 8.
+int cc_ref_gemm_sp24_f32(int device, const void* Ac, const void* Am,
+                         const void* Bt, void* C, int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0 || K % 8) return -2;
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  launch_ref_sp24(Ac, Am, Bt, C, M, N, K);
+  return (int)hipDeviceSynchronize();
+}
+
+// The opt-in sparse probe for one SMFMAC shape. gemm_dim below 128 rounds
+// up to 128, otherwise down to a multiple of 128. The report is
+// CcMxReport, unchanged: the caller knows the shape, and mx_tflops is the
+// dense-equivalent rate, 2 * D^3 over the time (the sparse core performs
+// half those multiplies). rep->ok = 1 iff the SMFMAC result equals the
+// VALU reference bitwise.
+int cc_attest_sparse(int device, int gemm_dim, int shape,
+                     struct CcMxReport* rep) {
+  CC_TRY(report_begin(rep, device, [&] {
+    if (shape == 0 || shape == 1) return 0;
+    snprintf(rep->error, sizeof(rep->error), "shape %d is not 0 or 1", shape);
+    return -2;
+  }));
+
+  const int D = gemm_dim < BKS ? BKS : (gemm_dim / BKS) * BKS;
+  rep->mx_m = rep->mx_n = rep->mx_k = D;
+
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  DeviceCtx& dev = device_ctx(device);
+  CC_CHECK(dev.events());
+  CC_CHECK(dev.sp24.acquire(D));
+  CC_TRY(probe_sparse(dev, shape, rep));
 
   rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
   return 0;

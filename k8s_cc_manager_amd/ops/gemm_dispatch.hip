@@ -322,3 +322,28 @@ static void launch_ref_f64(const void* A, const void* Bt, void* C, int M,
 // Largest dim of the FP64 leg: the fill's products are integers below 2^40,
 // so while K * 2^40 <= 2^53 every partial sum is exact in any order.
 constexpr int kF64ExactDim = 8192;
+
+// Launch the 2:4 sparse bf16 GEMM (no sync); shape 0 = the 32x32x32
+// SMFMAC, 1 = the 16x16x64 one, numbered as for launch_i8. -2 for any
+// other shape, M, N or K (the dense K) that does not fit the 128x128x128
+// tile, or operands that are not 16-byte aligned.
+static int launch_sp24(int shape, const void* Ac, const void* Am,
+                       const void* Bt, void* C, int M, int N, int K) {
+  if (shape != 0 && shape != 1) return -2;
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BKS) return -2;
+  if ((((uintptr_t)Ac | (uintptr_t)Am | (uintptr_t)Bt | (uintptr_t)C) & 15) != 0)
+    return -2;
+  auto kernel = shape == 0 ? mfma_gemm_sp24_128<0> : mfma_gemm_sp24_128<1>;
+  hipLaunchKernelGGL(kernel, dim3(N / BN, M / BM), dim3(256), 0, 0,
+                     (const char*)Ac, (const unsigned char*)Am,
+                     (const char*)Bt, (float*)C, M, N, K);
+  return 0;
+}
+
+static void launch_ref_sp24(const void* Ac, const void* Am, const void* Bt,
+                            void* C, int M, int N, int K) {
+  dim3 block(16, 16), grid((N + 15) / 16, (M + 15) / 16);
+  hipLaunchKernelGGL(ref_gemm_sp24_f32, grid, block, 0, 0, (const bf16*)Ac,
+                     (const unsigned char*)Am, (const bf16*)Bt, (float*)C, M,
+                     N, K);
+}

@@ -235,6 +235,35 @@ struct F64Ctx {
   }
 };
 
+// The sparse leg (cc_attest_sparse), same rules as MainCtx, keyed by dim
+// alone: both SMFMAC shapes read the same fill, so they share the cached
+// reference. 11.125 bytes per output element: compressed A (1), its index
+// (1/8), dense B (2), C and the reference (4 each).
+struct Sp24Ctx {
+  int dim = 0;
+  int ref_valid = 0;
+  DevBuf<bf16> dAc, dB;       // [D, D/2] kept values, [D, D] dense
+  DevBuf<unsigned char> dAm;  // [D, D/8] index nibbles
+  DevBuf<float> dC, dRef, dErr;
+  DevBuf<unsigned long long> dSum;
+
+  hipError_t acquire(int D) {
+    if (dim == D) return hipSuccess;
+    *this = Sp24Ctx{};
+    const size_t n = (size_t)D * D;
+    hipError_t e;
+    if ((e = dAc.ensure(n / 2 * sizeof(bf16))) ||
+        (e = dB.ensure(n * sizeof(bf16))) || (e = dAm.ensure(n / 8)) ||
+        (e = dC.ensure(n * sizeof(float))) ||
+        (e = dRef.ensure(n * sizeof(float))) ||
+        (e = dErr.ensure(sizeof(float))) ||
+        (e = dSum.ensure(sizeof(unsigned long long))))
+      return e;
+    dim = D;
+    return hipSuccess;
+  }
+};
+
 // The compute-unit sweep (cc_cu_sweep): fixed sizes, allocated once.
 struct SweepCtx {
   DevBuf<unsigned> dSweepTab;
@@ -282,6 +311,7 @@ struct DeviceCtx {
   Mx8Ctx mx8;
   I8Ctx i8;
   F64Ctx f64;
+  Sp24Ctx sp24;
   SweepCtx sweep;
   HbmCtx hbm;
   HostCtx host;

@@ -422,6 +422,78 @@ __global__ void max_abs_diff_f64(const double* __restrict__ x,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Sparse leg: fill and the VALU reference (data convention in
+// gemm_sp24.hip and docs/KERNELS.md, "Sparse leg"). The compare is
+// max_abs_diff.
+// ---------------------------------------------------------------------------
+// The six legal index nibbles (pos0 in bits 1:0 below pos1 in bits 3:2), one
+// per 4 bits: (0,1) (0,2) (0,3) (1,2) (1,3) (2,3).
+constexpr uint32_t kSp24Nibbles = 0xED9C84u;
+
+// nbytes index bytes of Am and the 4 * nbytes kept values of Ac they
+// govern. Values: the magnitudes {0, 0.5, 1, 1.5, 2, 3} with both signs
+// (-0 included), bf16 bits 0000 3f00 3f80 3fc0 4000 4040; nibbles: drawn
+// from the six legal ones. With am == nullptr it fills 4 * nbytes values
+// alone: the leg's dense B, from the same set. A product is then a
+// multiple of 2^-2 of at most 9 and a sum has K/2 terms, so every partial
+// sum fits 24 bits in any order while (K/2) * 36 < 2^24, and the SMFMAC
+// and VALU paths must agree bitwise.
+__global__ void fill_sp24_exact(bf16* __restrict__ vals,
+                                unsigned char* __restrict__ am, long nbytes,
+                                uint32_t seed) {
+  const unsigned long long mag = 0x404040003FC03F80ull;  // 1, 1.5, 2, 3
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+  for (; i < nbytes; i += stride) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      uint32_t x = (uint32_t)(4 * i + j) * 1103515245u + seed * 747796405u +
+                   12345u;
+      x ^= x >> 16;
+      x *= 2654435769u;
+      const unsigned r = (x >> 13) % 12u, m = r % 6u;
+      const unsigned bits = m == 0   ? 0u
+                            : m == 1 ? 0x3F00u
+                                     : (unsigned)(mag >> (16 * (m - 2))) & 0xFFFFu;
+      const unsigned short h = (unsigned short)(bits | (r / 6u) << 15);
+      vals[4 * i + j] = __builtin_bit_cast(bf16, h);
+    }
+    if (am) {
+      uint32_t x =
+          (uint32_t)i * 1103515245u + (seed + 64u) * 747796405u + 12345u;
+      x ^= x >> 16;
+      x *= 2654435769u;
+      const unsigned r = (x >> 13) % 36u;
+      am[i] = (unsigned char)(((kSp24Nibbles >> (4 * (r % 6u))) & 15u) |
+                              ((kSp24Nibbles >> (4 * (r / 6u))) & 15u) << 4);
+    }
+  }
+}
+
+// VALU 2:4 reference GEMM: one thread per C element. The nibble of every
+// group is decoded with integer shifts, literally (an illegal nibble reads
+// the positions it names); fp32 fma in k order (a product of two bf16 is
+// exact in fp32, so fusing changes nothing). No MFMA.
+__global__ void ref_gemm_sp24_f32(const bf16* __restrict__ Ac,
+                                  const unsigned char* __restrict__ Am,
+                                  const bf16* __restrict__ Bt,
+                                  float* __restrict__ C, int M, int N, int K) {
+  int col = blockIdx.x * blockDim.x + threadIdx.x;
+  int row = blockIdx.y * blockDim.y + threadIdx.y;
+  if (row >= M || col >= N) return;
+  const bf16* a = Ac + (long)row * (K / 2);
+  const unsigned char* am = Am + (long)row * (K / 8);
+  const bf16* b = Bt + (long)col * K;
+  float acc = 0.f;
+  for (int g = 0; g < K / 4; ++g) {
+    const unsigned nib = (am[g >> 1] >> (4 * (g & 1))) & 15u;
+    acc = fmaf((float)a[2 * g], (float)b[4 * g + (nib & 3u)], acc);
+    acc = fmaf((float)a[2 * g + 1], (float)b[4 * g + (nib >> 2)], acc);
+  }
+  C[(long)row * N + col] = acc;
+}
+
 // max |x-y| reduction over n elements -> out[0] (pre-zeroed)
 __global__ void max_abs_diff(const float* __restrict__ x,
                              const float* __restrict__ y, long n,

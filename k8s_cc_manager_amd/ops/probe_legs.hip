@@ -399,6 +399,39 @@ static int probe_fp64(DeviceCtx& dev, CcMxReport* rep) {
   return 0;
 }
 
+// Sparse leg: the exact value set (fill_sp24_exact) in compressed A and in
+// dense B, all six legal index nibbles, through the SMFMAC of `shape`
+// (0 = 32x32x32, 1 = 16x16x64), bitwise against the VALU reference, which
+// both shapes share. mx_tflops is the dense-equivalent rate, 2 * D^3 over
+// the time: the sparse core does half those multiplies.
+static int probe_sparse(DeviceCtx& dev, int shape, CcMxReport* rep) {
+  Sp24Ctx& ctx = dev.sp24;
+  const int D = ctx.dim;
+  const long elems = (long)D * D;
+  bf16 *dAc = ctx.dAc, *dB = ctx.dB;
+  unsigned char* dAm = ctx.dAm;
+  float *dC = ctx.dC, *dRef = ctx.dRef, *dErr = ctx.dErr;
+  unsigned long long* dSum = ctx.dSum;
+  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
+  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
+  // 0x7f7f7f7f: finite and huge, as in probe_mxfp4
+  CC_CHECK(hipMemset(dC, 0x7F, elems * sizeof(float)));
+
+  hipLaunchKernelGGL(fill_sp24_exact, dim3(2048), dim3(256), 0, 0, dAc, dAm,
+                     elems / 8, 1u);
+  hipLaunchKernelGGL(fill_sp24_exact, dim3(2048), dim3(256), 0, 0, dB,
+                     (unsigned char*)nullptr, elems / 4, 7u);
+
+  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops, [&] {
+    return launch_sp24(shape, dAc, dAm, dB, dC, D, D, D);
+  }));
+  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms, [&] {
+    launch_ref_sp24(dAc, dAm, dB, dRef, D, D, D);
+  }));
+  return compare_read_back(rep, dC, dRef, elems, dErr, &rep->mx_max_abs_err,
+                           dSum, &rep->mx_checksum);
+}
+
 // The golden C images for `rounds`, a constant: computed once per
 // (device, rounds). *ms = 0.0 when the cached images were used. `rep`
 // is whatever holds the error text (a report, or ErrorText).
