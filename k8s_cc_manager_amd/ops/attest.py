@@ -547,47 +547,61 @@ def attest_device(device_index: int, gemm_dim: int = 1024) -> AttestReport:
     return rep
 
 
+def _code(table: dict, what: str, value) -> int:
+    """A name from ``table`` or a number; a number goes to the library as
+    it is, which refuses what it does not know with -2."""
+    if isinstance(value, str):
+        if value not in table:
+            raise AttestationError(f"unknown {what} {value!r}")
+        return table[value]
+    return int(value)
+
+
+def _attest_exact(name: str, device_index: int, gemm_dim: int, codes=(),
+                  detail: str = "", unit: str = "TF/s",
+                  closing: str = "bitwise ok", log_name=None) -> MxReport:
+    """The body of the six exact-GEMM probes: call ``cc_attest_<name>``
+    with ``codes`` (format or shape numbers) between gemm_dim and the
+    report, raise on rc != 0 and on a report that is not ok, log one
+    line. ``detail`` names the codes in the messages."""
+    c = _CMxReport()
+    rc = getattr(_load(), "cc_attest_" + name)(
+        device_index, gemm_dim, *codes, ctypes.byref(c))
+    rep = MxReport.from_c(c)
+    if rc != 0:
+        raise AttestationError(
+            f"device {device_index}: {name} probe runtime error rc={rc}: {rep.error}"
+        )
+    if not rep.ok:
+        raise AttestationError(
+            f"device {device_index}: {name}{detail} attestation FAILED "
+            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
+        )
+    logger.info(
+        "attested device %d: %s%s GEMM %.1f %s (%dx%dx%d), %s",
+        rep.device,
+        log_name or name,
+        detail,
+        rep.mx_tflops,
+        unit,
+        rep.mx_dim,
+        rep.mx_dim,
+        rep.mx_dim,
+        closing,
+    )
+    return rep
+
+
 def attest_mxfp4(device_index: int, gemm_dim: int = 1024) -> MxReport:
     """Run the MXFP4 probe on one GPU: the fp4 MFMA GEMM with real E8M0
     block scales against the VALU reference, bitwise. Raises on failure.
     gemm_dim below 256 rounds up to 256, otherwise down to a multiple."""
-    lib = _load()
-    c = _CMxReport()
-    rc = lib.cc_attest_mxfp4(device_index, gemm_dim, ctypes.byref(c))
-    rep = MxReport.from_c(c)
-    if rc != 0:
-        raise AttestationError(
-            f"device {device_index}: mxfp4 probe runtime error rc={rc}: {rep.error}"
-        )
-    if not rep.ok:
-        raise AttestationError(
-            f"device {device_index}: mxfp4 attestation FAILED "
-            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
-        )
-    logger.info(
-        "attested device %d: mxfp4 GEMM %.1f TF/s (%dx%dx%d), bitwise ok",
-        rep.device,
-        rep.mx_tflops,
-        rep.mx_dim,
-        rep.mx_dim,
-        rep.mx_dim,
-    )
-    return rep
+    return _attest_exact("mxfp4", device_index, gemm_dim)
 
 
 # fp6 element formats by name; the numbers are the hardware's format
 # selector (cbsz / blgp), which the library takes as they are
 FP6_FORMATS = {"e2m3": 2, "e3m2": 3}
-
-
-def _fp6_fmt(fmt) -> int:
-    """"e2m3" / "e3m2" or a number; a number goes to the library as it
-    is, which refuses anything but 2 and 3 with -2."""
-    if isinstance(fmt, str):
-        if fmt not in FP6_FORMATS:
-            raise AttestationError(f"unknown fp6 format {fmt!r}")
-        return FP6_FORMATS[fmt]
-    return int(fmt)
 
 
 def attest_mxfp6(device_index: int, gemm_dim: int = 1024,
@@ -596,30 +610,9 @@ def attest_mxfp6(device_index: int, gemm_dim: int = 1024,
     "e3m2" or 2 / 3): the fp6 MFMA GEMM with real E8M0 block scales
     against the VALU reference, bitwise. Raises on failure. gemm_dim
     below 128 rounds up to 128, otherwise down to a multiple."""
-    lib = _load()
-    c = _CMxReport()
-    code = _fp6_fmt(fmt)
-    rc = lib.cc_attest_mxfp6(device_index, gemm_dim, code, ctypes.byref(c))
-    rep = MxReport.from_c(c)
-    if rc != 0:
-        raise AttestationError(
-            f"device {device_index}: mxfp6 probe runtime error rc={rc}: {rep.error}"
-        )
-    if not rep.ok:
-        raise AttestationError(
-            f"device {device_index}: mxfp6 fmt {code} attestation FAILED "
-            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
-        )
-    logger.info(
-        "attested device %d: mxfp6 fmt %d GEMM %.1f TF/s (%dx%dx%d), bitwise ok",
-        rep.device,
-        code,
-        rep.mx_tflops,
-        rep.mx_dim,
-        rep.mx_dim,
-        rep.mx_dim,
-    )
-    return rep
+    code = _code(FP6_FORMATS, "fp6 format", fmt)
+    return _attest_exact("mxfp6", device_index, gemm_dim, (code,),
+                         f" fmt {code}")
 
 
 # fp8 element formats by name; the numbers are the hardware's format
@@ -627,14 +620,10 @@ def attest_mxfp6(device_index: int, gemm_dim: int = 1024,
 FP8_FORMATS = {"e4m3": 0, "e5m2": 1}
 
 
-def _fp8_fmt(fmt) -> int:
-    """"e4m3" / "e5m2" or a number; a number goes to the library as it
-    is, which refuses anything but 0 and 1 with -2."""
-    if isinstance(fmt, str):
-        if fmt not in FP8_FORMATS:
-            raise AttestationError(f"unknown fp8 format {fmt!r}")
-        return FP8_FORMATS[fmt]
-    return int(fmt)
+def _fp8_pair(fmt_a, fmt_b) -> tuple:
+    """The numbers of a format pair; ``fmt_b`` None means A's format."""
+    fa = _code(FP8_FORMATS, "fp8 format", fmt_a)
+    return fa, fa if fmt_b is None else _code(FP8_FORMATS, "fp8 format", fmt_b)
 
 
 def attest_mxfp8(device_index: int, gemm_dim: int = 1024, fmt_a="e4m3",
@@ -644,33 +633,9 @@ def attest_mxfp8(device_index: int, gemm_dim: int = 1024, fmt_a="e4m3",
     fp8 MFMA GEMM with real E8M0 block scales against the VALU reference,
     bitwise. Raises on failure. gemm_dim below 128 rounds up to 128,
     otherwise down to a multiple."""
-    lib = _load()
-    c = _CMxReport()
-    fa = _fp8_fmt(fmt_a)
-    fb = fa if fmt_b is None else _fp8_fmt(fmt_b)
-    rc = lib.cc_attest_mxfp8(device_index, gemm_dim, fa, fb, ctypes.byref(c))
-    rep = MxReport.from_c(c)
-    if rc != 0:
-        raise AttestationError(
-            f"device {device_index}: mxfp8 probe runtime error rc={rc}: {rep.error}"
-        )
-    if not rep.ok:
-        raise AttestationError(
-            f"device {device_index}: mxfp8 fmt ({fa}, {fb}) attestation FAILED "
-            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
-        )
-    logger.info(
-        "attested device %d: mxfp8 fmt (%d, %d) GEMM %.1f TF/s (%dx%dx%d), "
-        "bitwise ok",
-        rep.device,
-        fa,
-        fb,
-        rep.mx_tflops,
-        rep.mx_dim,
-        rep.mx_dim,
-        rep.mx_dim,
-    )
-    return rep
+    fa, fb = _fp8_pair(fmt_a, fmt_b)
+    return _attest_exact("mxfp8", device_index, gemm_dim, (fa, fb),
+                         f" fmt ({fa}, {fb})")
 
 
 # the format pairs the attestor hook runs: each decoder on each operand
@@ -682,16 +647,6 @@ MXFP8_HOOK_PAIRS = (("e4m3", "e5m2"), ("e5m2", "e4m3"))
 INT8_SHAPES = {"32x32x32": 0, "16x16x64": 1}
 
 
-def _i8_shape(shape) -> int:
-    """"32x32x32" / "16x16x64" or a number; a number goes to the library
-    as it is, which refuses anything but 0 and 1 with -2."""
-    if isinstance(shape, str):
-        if shape not in INT8_SHAPES:
-            raise AttestationError(f"unknown int8 MFMA shape {shape!r}")
-        return INT8_SHAPES[shape]
-    return int(shape)
-
-
 def attest_int8(device_index: int, gemm_dim: int = 1024,
                 shape="32x32x32") -> MxReport:
     """Run the INT8 probe on one GPU for one integer MFMA shape
@@ -700,31 +655,9 @@ def attest_int8(device_index: int, gemm_dim: int = 1024,
     MxReport: ``mx_tflops`` carries TOP/s and ``mx_max_abs_err`` the
     largest |C - ref|, computed in integers. Raises on failure. gemm_dim
     below 128 rounds up to 128, otherwise down to a multiple."""
-    lib = _load()
-    c = _CMxReport()
-    code = _i8_shape(shape)
-    rc = lib.cc_attest_int8(device_index, gemm_dim, code, ctypes.byref(c))
-    rep = MxReport.from_c(c)
-    if rc != 0:
-        raise AttestationError(
-            f"device {device_index}: int8 probe runtime error rc={rc}: {rep.error}"
-        )
-    if not rep.ok:
-        raise AttestationError(
-            f"device {device_index}: int8 shape {code} attestation FAILED "
-            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
-        )
-    logger.info(
-        "attested device %d: int8 shape %d GEMM %.1f TOP/s (%dx%dx%d), "
-        "bitwise ok",
-        rep.device,
-        code,
-        rep.mx_tflops,
-        rep.mx_dim,
-        rep.mx_dim,
-        rep.mx_dim,
-    )
-    return rep
+    code = _code(INT8_SHAPES, "int8 MFMA shape", shape)
+    return _attest_exact("int8", device_index, gemm_dim, (code,),
+                         f" shape {code}", unit="TOP/s")
 
 
 def attest_fp64(device_index: int, gemm_dim: int = 1024) -> MxReport:
@@ -735,28 +668,7 @@ def attest_fp64(device_index: int, gemm_dim: int = 1024) -> MxReport:
     NaN counts as infinity). Raises on failure. gemm_dim below 128 rounds
     up to 128, otherwise down to a multiple; above 8192 (K * 2^40 must
     stay within 2^53) the library refuses it with rc=-2."""
-    lib = _load()
-    c = _CMxReport()
-    rc = lib.cc_attest_fp64(device_index, gemm_dim, ctypes.byref(c))
-    rep = MxReport.from_c(c)
-    if rc != 0:
-        raise AttestationError(
-            f"device {device_index}: fp64 probe runtime error rc={rc}: {rep.error}"
-        )
-    if not rep.ok:
-        raise AttestationError(
-            f"device {device_index}: fp64 attestation FAILED "
-            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
-        )
-    logger.info(
-        "attested device %d: fp64 GEMM %.1f TF/s (%dx%dx%d), exact",
-        rep.device,
-        rep.mx_tflops,
-        rep.mx_dim,
-        rep.mx_dim,
-        rep.mx_dim,
-    )
-    return rep
+    return _attest_exact("fp64", device_index, gemm_dim, closing="exact")
 
 
 # the bf16 SMFMAC shapes of the sparse leg by name, numbered as INT8_SHAPES
@@ -765,16 +677,6 @@ SPARSE_SHAPES = {"32x32x32": 0, "16x16x64": 1}
 # the six legal 2:4 index nibbles, pos0 in bits 1:0 below pos1 in bits 3:2:
 # (0,1) (0,2) (0,3) (1,2) (1,3) (2,3)
 SP24_NIBBLES = (0x4, 0x8, 0xC, 0x9, 0xD, 0xE)
-
-
-def _sparse_shape(shape) -> int:
-    """"32x32x32" / "16x16x64" or a number; a number goes to the library
-    as it is, which refuses anything but 0 and 1 with -2."""
-    if isinstance(shape, str):
-        if shape not in SPARSE_SHAPES:
-            raise AttestationError(f"unknown sparse MFMA shape {shape!r}")
-        return SPARSE_SHAPES[shape]
-    return int(shape)
 
 
 def sp24_dense(ac, am):
@@ -805,31 +707,10 @@ def attest_sparse(device_index: int, gemm_dim: int = 1024,
     dense-equivalent rate, 2 * dim^3 over the time (the sparse core
     performs half those multiplies). Raises on failure. gemm_dim below 128
     rounds up to 128, otherwise down to a multiple."""
-    lib = _load()
-    c = _CMxReport()
-    code = _sparse_shape(shape)
-    rc = lib.cc_attest_sparse(device_index, gemm_dim, code, ctypes.byref(c))
-    rep = MxReport.from_c(c)
-    if rc != 0:
-        raise AttestationError(
-            f"device {device_index}: sparse probe runtime error rc={rc}: {rep.error}"
-        )
-    if not rep.ok:
-        raise AttestationError(
-            f"device {device_index}: sparse shape {code} attestation FAILED "
-            f"(mx_max_abs_err={rep.mx_max_abs_err}, mx_tflops={rep.mx_tflops})"
-        )
-    logger.info(
-        "attested device %d: 2:4 sparse bf16 shape %d GEMM %.1f TF/s "
-        "dense-equivalent (%dx%dx%d), bitwise ok",
-        rep.device,
-        code,
-        rep.mx_tflops,
-        rep.mx_dim,
-        rep.mx_dim,
-        rep.mx_dim,
-    )
-    return rep
+    code = _code(SPARSE_SHAPES, "sparse MFMA shape", shape)
+    return _attest_exact("sparse", device_index, gemm_dim, (code,),
+                         f" shape {code}", unit="TF/s dense-equivalent",
+                         log_name="2:4 sparse bf16")
 
 
 CU_SWEEP_MAX_ROUNDS = 256  # exactness cap of the sweep's MFMA chains
@@ -1203,6 +1084,25 @@ def device_index_for_bdf(bdf: str) -> int:
     return idx
 
 
+# The opt-in exact-GEMM legs of the attestor hook, in the order they run
+# and appear in the summary: the switch (CC_ATTEST_<switch>=1), the
+# function, its keyword arguments for each call, and the summary keys for
+# the lowest rate of those calls and for "every call agreed".
+_HOOK_EXACT_LEGS = (
+    ("MXFP4", "attest_mxfp4", [{}], "mxfp4_tflops", "mxfp4_bitwise_ok"),
+    ("MXFP6", "attest_mxfp6", [{"fmt": f} for f in FP6_FORMATS],
+     "mxfp6_tflops", "mxfp6_bitwise_ok"),
+    ("MXFP8", "attest_mxfp8",
+     [{"fmt_a": fa, "fmt_b": fb} for fa, fb in MXFP8_HOOK_PAIRS],
+     "mxfp8_tflops", "mxfp8_bitwise_ok"),
+    ("INT8", "attest_int8", [{"shape": s} for s in INT8_SHAPES],
+     "int8_tops", "int8_bitwise_ok"),
+    ("FP64", "attest_fp64", [{}], "fp64_tflops", "fp64_exact_ok"),
+    ("SPARSE", "attest_sparse", [{"shape": s} for s in SPARSE_SHAPES],
+     "sparse_tflops", "sparse_bitwise_ok"),
+)
+
+
 def attest_device_by_bdf(device) -> dict:
     """TransitionEngine attestor hook: CCDevice -> evidence summary
     (raises on failure).
@@ -1223,26 +1123,11 @@ def attest_device_by_bdf(device) -> dict:
 
         deep_attest_device(idx, gemm_dim=gemm_dim)
         deep = True
-    mx = None
-    if os.environ.get("CC_ATTEST_MXFP4", "0") == "1":
-        mx = attest_mxfp4(idx, gemm_dim=gemm_dim)
-    mx6 = None
-    if os.environ.get("CC_ATTEST_MXFP6", "0") == "1":
-        mx6 = [attest_mxfp6(idx, gemm_dim=gemm_dim, fmt=f) for f in FP6_FORMATS]
-    mx8 = None
-    if os.environ.get("CC_ATTEST_MXFP8", "0") == "1":
-        mx8 = [attest_mxfp8(idx, gemm_dim=gemm_dim, fmt_a=fa, fmt_b=fb)
-               for fa, fb in MXFP8_HOOK_PAIRS]
-    i8 = None
-    if os.environ.get("CC_ATTEST_INT8", "0") == "1":
-        i8 = [attest_int8(idx, gemm_dim=gemm_dim, shape=s) for s in INT8_SHAPES]
-    f64 = None
-    if os.environ.get("CC_ATTEST_FP64", "0") == "1":
-        f64 = attest_fp64(idx, gemm_dim=gemm_dim)
-    sp = None
-    if os.environ.get("CC_ATTEST_SPARSE", "0") == "1":
-        sp = [attest_sparse(idx, gemm_dim=gemm_dim, shape=s)
-              for s in SPARSE_SHAPES]
+    # the module's attribute at call time: a test's stub is what runs
+    exact = [(rate_key, ok_key,
+              [globals()[fn](idx, gemm_dim=gemm_dim, **kw) for kw in calls])
+             for switch, fn, calls, rate_key, ok_key in _HOOK_EXACT_LEGS
+             if os.environ.get("CC_ATTEST_" + switch, "0") == "1"]
     sweep = None
     if os.environ.get("CC_ATTEST_CU_SWEEP", "0") == "1":
         sweep = sweep_compute_units(idx)
@@ -1279,24 +1164,9 @@ def attest_device_by_bdf(device) -> dict:
         ]
     if deep:
         summary["deep_pmc"] = True
-    if mx is not None:
-        summary["mxfp4_tflops"] = round(mx.mx_tflops, 1)
-        summary["mxfp4_bitwise_ok"] = mx.mx_max_abs_err == 0.0
-    if mx6 is not None:
-        summary["mxfp6_tflops"] = round(min(r.mx_tflops for r in mx6), 1)
-        summary["mxfp6_bitwise_ok"] = all(r.mx_max_abs_err == 0.0 for r in mx6)
-    if mx8 is not None:
-        summary["mxfp8_tflops"] = round(min(r.mx_tflops for r in mx8), 1)
-        summary["mxfp8_bitwise_ok"] = all(r.mx_max_abs_err == 0.0 for r in mx8)
-    if i8 is not None:
-        summary["int8_tops"] = round(min(r.mx_tflops for r in i8), 1)
-        summary["int8_bitwise_ok"] = all(r.mx_max_abs_err == 0.0 for r in i8)
-    if f64 is not None:
-        summary["fp64_tflops"] = round(f64.mx_tflops, 1)
-        summary["fp64_exact_ok"] = f64.mx_max_abs_err == 0.0
-    if sp is not None:
-        summary["sparse_tflops"] = round(min(r.mx_tflops for r in sp), 1)
-        summary["sparse_bitwise_ok"] = all(r.mx_max_abs_err == 0.0 for r in sp)
+    for rate_key, ok_key, reps in exact:
+        summary[rate_key] = round(min(r.mx_tflops for r in reps), 1)
+        summary[ok_key] = all(r.mx_max_abs_err == 0.0 for r in reps)
     if sweep is not None:
         summary["cu_sweep"] = f"{sweep.units_seen}/{sweep.units_expected}"
         summary["cu_sweep_ok"] = sweep.ok
@@ -1399,7 +1269,8 @@ def mfma_gemm_mxfp6(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
     SB uint8 E8M0 [rows, K/32]. M,N and K multiples of 128, 16-byte
     aligned pointers; anything else raises with rc=-2."""
     _gemm_call("cc_mfma_gemm_mxfp6", "mfma_gemm_mxfp6", device_index, a_ptr,
-               sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k, _fp6_fmt(fmt))
+               sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k,
+               _code(FP6_FORMATS, "fp6 format", fmt))
 
 
 def ref_gemm_mxfp6_f32(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
@@ -1408,7 +1279,8 @@ def ref_gemm_mxfp6_f32(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
     """VALU reference of :func:`mfma_gemm_mxfp6` (integer field extraction
     and decode, ldexpf scales, no MFMA): any M and N, K a multiple of 32."""
     _gemm_call("cc_ref_gemm_mxfp6_f32", "ref_gemm_mxfp6_f32", device_index,
-               a_ptr, sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k, _fp6_fmt(fmt))
+               a_ptr, sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k,
+               _code(FP6_FORMATS, "fp6 format", fmt))
 
 
 def mfma_gemm_mxfp8(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
@@ -1419,10 +1291,9 @@ def mfma_gemm_mxfp8(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
     independently; ``fmt_b`` None means A's format. A[M,K] and Bt[N,K]
     uint8 OCP codes, SA and SB uint8 E8M0 [rows, K/32]. M,N and K multiples
     of 128, 16-byte aligned pointers; anything else raises with rc=-2."""
-    fa = _fp8_fmt(fmt_a)
     _gemm_call("cc_mfma_gemm_mxfp8", "mfma_gemm_mxfp8", device_index, a_ptr,
-               sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k, fa,
-               fa if fmt_b is None else _fp8_fmt(fmt_b))
+               sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k,
+               *_fp8_pair(fmt_a, fmt_b))
 
 
 def mfma_gemm_i8(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
@@ -1433,7 +1304,7 @@ def mfma_gemm_i8(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
     (no sum can leave 32 bits), 16-byte aligned pointers; anything else
     raises with rc=-2."""
     _gemm_call("cc_mfma_gemm_i8", "mfma_gemm_i8", device_index, a_ptr, bt_ptr,
-               c_ptr, m, n, k, _i8_shape(shape))
+               c_ptr, m, n, k, _code(INT8_SHAPES, "int8 MFMA shape", shape))
 
 
 def ref_gemm_i8_i32(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
@@ -1471,7 +1342,8 @@ def mfma_gemm_sp24(device_index: int, ac_ptr: int, am_ptr: int, bt_ptr: int,
     (0) or "16x16x64" (1) picks the SMFMAC. M, N and K multiples of 128,
     16-byte aligned pointers; anything else raises with rc=-2."""
     _gemm_call("cc_mfma_gemm_sp24", "mfma_gemm_sp24", device_index, ac_ptr,
-               am_ptr, bt_ptr, c_ptr, m, n, k, _sparse_shape(shape))
+               am_ptr, bt_ptr, c_ptr, m, n, k,
+               _code(SPARSE_SHAPES, "sparse MFMA shape", shape))
 
 
 def ref_gemm_sp24_f32(device_index: int, ac_ptr: int, am_ptr: int, bt_ptr: int,
@@ -1487,7 +1359,6 @@ def ref_gemm_mxfp8_f32(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,
                        fmt_a="e4m3", fmt_b=None) -> None:
     """VALU reference of :func:`mfma_gemm_mxfp8` (integer field extraction,
     ldexpf decode and scales, no MFMA): any M and N, K a multiple of 32."""
-    fa = _fp8_fmt(fmt_a)
     _gemm_call("cc_ref_gemm_mxfp8_f32", "ref_gemm_mxfp8_f32", device_index,
-               a_ptr, sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k, fa,
-               fa if fmt_b is None else _fp8_fmt(fmt_b))
+               a_ptr, sa_ptr, bt_ptr, sb_ptr, c_ptr, m, n, k,
+               *_fp8_pair(fmt_a, fmt_b))

@@ -57,10 +57,14 @@
 //   probe_reports.hip  the five report structs (frozen layouts);
 //   gemm_dispatch.hip  named variants, launchers, production dispatch;
 //   probe_ctx.hip      CC_CHECK / CC_TRY, DevBuf, the per-leg contexts of
-//                      a DeviceCtx, timed_ms, read_back, DeviceHop;
+//                      a DeviceCtx (one type, ExactCtx, for the six
+//                      exact-GEMM legs, with their description ExactLeg),
+//                      timed_ms, read_back, DeviceHop;
 //   host_pattern.hip   the CPU fill and compare of the host-link leg
 //                      (plain C++, no HIP call);
-//   probe_legs.hip     the fifteen legs and the steps the GEMM legs share.
+//   probe_legs.hip     the fifteen legs (six of them one routine,
+//                      probe_exact, and an ExactLeg each) and the steps the
+//                      GEMM legs share.
 //
 // cc_attest_device runs five legs in order:
 //   1. probe_bf16  — production bf16 GEMM dispatch, timed, compared
@@ -157,6 +161,30 @@ static int hbm_refuse_range(Report* rep, unsigned long long origin,
   return -2;
 }
 
+// What the six exact-GEMM probes do once `refuse` has passed (still before
+// the device is touched): round gemm_dim to the leg's granule, take the
+// lock, the events and the leg's context for (D, key), run the leg.
+// rep->ok = 1 iff the result equals the reference and the GEMM was timed.
+template <typename Refuse>
+static int attest_exact(const ExactLeg& leg, int device, int gemm_dim,
+                        ExactKey key, int variant, CcMxReport* rep,
+                        Refuse refuse) {
+  CC_TRY(report_begin(rep, device, refuse));
+
+  const int G = leg.granule;
+  const int D = gemm_dim < G ? G : (gemm_dim / G) * G;
+  rep->mx_m = rep->mx_n = rep->mx_k = D;
+
+  std::lock_guard<std::mutex> lk(g_ctx_mu);
+  DeviceCtx& dev = device_ctx(device);
+  CC_CHECK(dev.events());
+  CC_CHECK((dev.*leg.ctx).acquire(leg, D, key));
+  CC_TRY(probe_exact(dev, leg, variant, rep));
+
+  rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
+  return 0;
+}
+
 extern "C" {
 
 int cc_device_alive(int device) {
@@ -203,10 +231,8 @@ int cc_device_index_for_bdf(int domain, int bus, int dev) {
 // block per CU).
 int cc_mfma_gemm_bf16(int device, const void* A, const void* Bt, void* C,
                       int M, int N, int K) {
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  int rc = launch_mfma_gemm(A, Bt, C, M, N, K);
-  if (rc != 0) return rc;
-  return (int)hipDeviceSynchronize();
+  return run_synced(device,
+                    [&] { return launch_mfma_gemm(A, Bt, C, M, N, K); });
 }
 
 // Force a specific bf16 variant (perf characterization / A-B); `which`
@@ -230,21 +256,20 @@ int cc_mfma_gemm_fp8_variant(int device, const void* A, const void* Bt,
 // fp32 out. M,N multiples of 128; K multiple of 64.
 int cc_mfma_gemm_fp8(int device, const void* A, const void* Bt, void* C,
                      int M, int N, int K) {
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  int rc = launch_fp8_best(A, Bt, C, M, N, K);
-  if (rc != 0) return rc;
-  return (int)hipDeviceSynchronize();
+  return run_synced(device,
+                    [&] { return launch_fp8_best(A, Bt, C, M, N, K); });
 }
 
 // Plain fp32 reference GEMM on the same operand convention.
 int cc_ref_gemm_f32(int device, const void* A, const void* Bt, void* C,
                     int M, int N, int K) {
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  dim3 block(16, 16);
-  dim3 grid((N + 15) / 16, (M + 15) / 16);
-  hipLaunchKernelGGL(ref_gemm_f32, grid, block, 0, 0, (const bf16*)A,
-                     (const bf16*)Bt, (float*)C, M, N, K);
-  return (int)hipDeviceSynchronize();
+  return run_synced(device, [&] {
+    dim3 block(16, 16);
+    dim3 grid((N + 15) / 16, (M + 15) / 16);
+    hipLaunchKernelGGL(ref_gemm_f32, grid, block, 0, 0, (const bf16*)A,
+                       (const bf16*)Bt, (float*)C, M, N, K);
+    return 0;
+  });
 }
 
 // The full self-contained attestation probe. gemm_dim: problem size
@@ -293,10 +318,8 @@ int cc_report_sizeof(void) { return (int)sizeof(struct CcAttestReport); }
 int cc_mfma_gemm_mxfp4(int device, const void* A, const void* SA,
                        const void* Bt, const void* SB, void* C, int M, int N,
                        int K) {
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  int rc = launch_mxfp4(A, SA, Bt, SB, C, M, N, K);
-  if (rc != 0) return rc;
-  return (int)hipDeviceSynchronize();
+  return run_synced(
+      device, [&] { return launch_mxfp4(A, SA, Bt, SB, C, M, N, K); });
 }
 
 // VALU reference of the same convention: any M and N, K a multiple of 32.
@@ -304,28 +327,18 @@ int cc_ref_gemm_mxfp4_f32(int device, const void* A, const void* SA,
                           const void* Bt, const void* SB, void* C, int M,
                           int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0 || K % 32) return -2;
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  launch_ref_mxfp4(A, SA, Bt, SB, C, M, N, K);
-  return (int)hipDeviceSynchronize();
+  return run_synced(device, [&] {
+    launch_ref_mxfp4(A, SA, Bt, SB, C, M, N, K);
+    return 0;
+  });
 }
 
 // The opt-in MXFP4 probe. gemm_dim below 256 rounds up to 256, otherwise
 // down to a multiple of 256. rep->ok = 1 iff the MFMA result equals the
 // VALU reference bitwise.
 int cc_attest_mxfp4(int device, int gemm_dim, struct CcMxReport* rep) {
-  CC_TRY(report_begin(rep, device));
-
-  const int D = gemm_dim < BK4 ? BK4 : (gemm_dim / BK4) * BK4;
-  rep->mx_m = rep->mx_n = rep->mx_k = D;
-
-  std::lock_guard<std::mutex> lk(g_ctx_mu);
-  DeviceCtx& dev = device_ctx(device);
-  CC_CHECK(dev.events());
-  CC_CHECK(dev.mx.acquire(D));
-  CC_TRY(probe_mxfp4(dev, rep));
-
-  rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
-  return 0;
+  return attest_exact(kLegMxfp4, device, gemm_dim, {}, 0, rep,
+                      [] { return 0; });
 }
 
 // MXFP6 GEMM on caller-provided device buffers (layout in
@@ -336,10 +349,8 @@ int cc_attest_mxfp4(int device, int gemm_dim, struct CcMxReport* rep) {
 int cc_mfma_gemm_mxfp6(int device, const void* A, const void* SA,
                        const void* Bt, const void* SB, void* C, int M, int N,
                        int K, int fmt) {
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  int rc = launch_mxfp6(fmt, A, SA, Bt, SB, C, M, N, K);
-  if (rc != 0) return rc;
-  return (int)hipDeviceSynchronize();
+  return run_synced(
+      device, [&] { return launch_mxfp6(fmt, A, SA, Bt, SB, C, M, N, K); });
 }
 
 // VALU reference of the same convention: any M and N, K a multiple of 32.
@@ -348,9 +359,10 @@ int cc_ref_gemm_mxfp6_f32(int device, const void* A, const void* SA,
                           int N, int K, int fmt) {
   if (M <= 0 || N <= 0 || K <= 0 || K % 32 || (fmt != 2 && fmt != 3))
     return -2;
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  launch_ref_mxfp6(fmt, A, SA, Bt, SB, C, M, N, K);
-  return (int)hipDeviceSynchronize();
+  return run_synced(device, [&] {
+    launch_ref_mxfp6(fmt, A, SA, Bt, SB, C, M, N, K);
+    return 0;
+  });
 }
 
 // The opt-in MXFP6 probe for one format. gemm_dim below 128 rounds up to
@@ -358,23 +370,11 @@ int cc_ref_gemm_mxfp6_f32(int device, const void* A, const void* SA,
 // unchanged: the caller knows fmt. rep->ok = 1 iff the MFMA result
 // equals the VALU reference bitwise.
 int cc_attest_mxfp6(int device, int gemm_dim, int fmt, struct CcMxReport* rep) {
-  CC_TRY(report_begin(rep, device, [&] {
+  return attest_exact(kLegMxfp6, device, gemm_dim, {fmt}, 0, rep, [&] {
     if (fmt == 2 || fmt == 3) return 0;
     snprintf(rep->error, sizeof(rep->error), "fmt %d is not 2 or 3", fmt);
     return -2;
-  }));
-
-  const int D = gemm_dim < BK6 ? BK6 : (gemm_dim / BK6) * BK6;
-  rep->mx_m = rep->mx_n = rep->mx_k = D;
-
-  std::lock_guard<std::mutex> lk(g_ctx_mu);
-  DeviceCtx& dev = device_ctx(device);
-  CC_CHECK(dev.events());
-  CC_CHECK(dev.mx6.acquire(D, fmt));
-  CC_TRY(probe_mxfp6(dev, rep));
-
-  rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
-  return 0;
+  });
 }
 
 // MXFP8 GEMM on caller-provided device buffers (layout in
@@ -385,10 +385,9 @@ int cc_attest_mxfp6(int device, int gemm_dim, int fmt, struct CcMxReport* rep) {
 int cc_mfma_gemm_mxfp8(int device, const void* A, const void* SA,
                        const void* Bt, const void* SB, void* C, int M, int N,
                        int K, int fmt_a, int fmt_b) {
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  int rc = launch_mxfp8(fmt_a, fmt_b, A, SA, Bt, SB, C, M, N, K);
-  if (rc != 0) return rc;
-  return (int)hipDeviceSynchronize();
+  return run_synced(device, [&] {
+    return launch_mxfp8(fmt_a, fmt_b, A, SA, Bt, SB, C, M, N, K);
+  });
 }
 
 // VALU reference of the same convention: any M and N, K a multiple of 32.
@@ -398,9 +397,10 @@ int cc_ref_gemm_mxfp8_f32(int device, const void* A, const void* SA,
   if (M <= 0 || N <= 0 || K <= 0 || K % 32 || (fmt_a != 0 && fmt_a != 1) ||
       (fmt_b != 0 && fmt_b != 1))
     return -2;
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  launch_ref_mxfp8(fmt_a, fmt_b, A, SA, Bt, SB, C, M, N, K);
-  return (int)hipDeviceSynchronize();
+  return run_synced(device, [&] {
+    launch_ref_mxfp8(fmt_a, fmt_b, A, SA, Bt, SB, C, M, N, K);
+    return 0;
+  });
 }
 
 // The opt-in MXFP8 probe for one format pair. gemm_dim below 128 rounds
@@ -409,24 +409,13 @@ int cc_ref_gemm_mxfp8_f32(int device, const void* A, const void* SA,
 // MFMA result equals the VALU reference bitwise.
 int cc_attest_mxfp8(int device, int gemm_dim, int fmt_a, int fmt_b,
                     struct CcMxReport* rep) {
-  CC_TRY(report_begin(rep, device, [&] {
+  const ExactKey key = {fmt_a, fmt_b};
+  return attest_exact(kLegMxfp8, device, gemm_dim, key, 0, rep, [&] {
     if ((fmt_a == 0 || fmt_a == 1) && (fmt_b == 0 || fmt_b == 1)) return 0;
     snprintf(rep->error, sizeof(rep->error), "fmt_a %d or fmt_b %d is not 0 or 1",
              fmt_a, fmt_b);
     return -2;
-  }));
-
-  const int D = gemm_dim < BK8 ? BK8 : (gemm_dim / BK8) * BK8;
-  rep->mx_m = rep->mx_n = rep->mx_k = D;
-
-  std::lock_guard<std::mutex> lk(g_ctx_mu);
-  DeviceCtx& dev = device_ctx(device);
-  CC_CHECK(dev.events());
-  CC_CHECK(dev.mx8.acquire(D, fmt_a, fmt_b));
-  CC_TRY(probe_mxfp8(dev, rep));
-
-  rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
-  return 0;
+  });
 }
 
 // INT8 GEMM on caller-provided device buffers (layout in gemm_i8.hip):
@@ -435,19 +424,18 @@ int cc_attest_mxfp8(int device, int gemm_dim, int fmt_a, int fmt_b,
 // 16-byte aligned; anything else returns -2 without launching.
 int cc_mfma_gemm_i8(int device, const void* A, const void* Bt, void* C, int M,
                     int N, int K, int shape) {
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  int rc = launch_i8(shape, A, Bt, C, M, N, K);
-  if (rc != 0) return rc;
-  return (int)hipDeviceSynchronize();
+  return run_synced(device,
+                    [&] { return launch_i8(shape, A, Bt, C, M, N, K); });
 }
 
 // VALU reference of the same convention: any M and N, K at most 130944.
 int cc_ref_gemm_i8_i32(int device, const void* A, const void* Bt, void* C,
                        int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0 || K > kI8MaxK) return -2;
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  launch_ref_i8(A, Bt, C, M, N, K);
-  return (int)hipDeviceSynchronize();
+  return run_synced(device, [&] {
+    launch_ref_i8(A, Bt, C, M, N, K);
+    return 0;
+  });
 }
 
 // The opt-in INT8 probe for one MFMA shape. gemm_dim below 128 rounds up
@@ -458,25 +446,13 @@ int cc_ref_gemm_i8_i32(int device, const void* A, const void* Bt, void* C,
 // reference bitwise.
 int cc_attest_int8(int device, int gemm_dim, int shape,
                    struct CcMxReport* rep) {
-  CC_TRY(report_begin(rep, device, [&] {
+  return attest_exact(kLegInt8, device, gemm_dim, {}, shape, rep, [&] {
     if ((shape == 0 || shape == 1) && gemm_dim <= kI8MaxK) return 0;
     snprintf(rep->error, sizeof(rep->error),
              "shape %d is not 0 or 1, or gemm_dim %d above %d", shape,
              gemm_dim, kI8MaxK);
     return -2;
-  }));
-
-  const int D = gemm_dim < BK8 ? BK8 : (gemm_dim / BK8) * BK8;
-  rep->mx_m = rep->mx_n = rep->mx_k = D;
-
-  std::lock_guard<std::mutex> lk(g_ctx_mu);
-  DeviceCtx& dev = device_ctx(device);
-  CC_CHECK(dev.events());
-  CC_CHECK(dev.i8.acquire(D));
-  CC_TRY(probe_int8(dev, shape, rep));
-
-  rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
-  return 0;
+  });
 }
 
 // FP64 GEMM on caller-provided device buffers (layout in gemm_f64.hip):
@@ -484,10 +460,7 @@ int cc_attest_int8(int device, int gemm_dim, int shape,
 // 16, pointers 16-byte aligned; anything else returns -2 without launching.
 int cc_mfma_gemm_f64(int device, const void* A, const void* Bt, void* C, int M,
                      int N, int K) {
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  int rc = launch_f64(A, Bt, C, M, N, K);
-  if (rc != 0) return rc;
-  return (int)hipDeviceSynchronize();
+  return run_synced(device, [&] { return launch_f64(A, Bt, C, M, N, K); });
 }
 
 // VALU reference of the same convention (fma in double, k order): any M,
@@ -495,9 +468,10 @@ int cc_mfma_gemm_f64(int device, const void* A, const void* Bt, void* C, int M,
 int cc_ref_gemm_f64(int device, const void* A, const void* Bt, void* C, int M,
                     int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0) return -2;
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  launch_ref_f64(A, Bt, C, M, N, K);
-  return (int)hipDeviceSynchronize();
+  return run_synced(device, [&] {
+    launch_ref_f64(A, Bt, C, M, N, K);
+    return 0;
+  });
 }
 
 // The opt-in FP64 probe. gemm_dim below 128 rounds up to 128, otherwise
@@ -506,25 +480,13 @@ int cc_ref_gemm_f64(int device, const void* A, const void* Bt, void* C, int M,
 // unchanged: mx_max_abs_err carries the largest |C - ref|, taken in
 // double. rep->ok = 1 iff the MFMA result equals the VALU reference.
 int cc_attest_fp64(int device, int gemm_dim, struct CcMxReport* rep) {
-  CC_TRY(report_begin(rep, device, [&] {
+  return attest_exact(kLegFp64, device, gemm_dim, {}, 0, rep, [&] {
     if (gemm_dim <= kF64ExactDim) return 0;
     snprintf(rep->error, sizeof(rep->error),
              "gemm_dim %d above %d: the fp64 leg's sums would not be exact",
              gemm_dim, kF64ExactDim);
     return -2;
-  }));
-
-  const int D = gemm_dim < BM ? BM : (gemm_dim / BM) * BM;
-  rep->mx_m = rep->mx_n = rep->mx_k = D;
-
-  std::lock_guard<std::mutex> lk(g_ctx_mu);
-  DeviceCtx& dev = device_ctx(device);
-  CC_CHECK(dev.events());
-  CC_CHECK(dev.f64.acquire(D));
-  CC_TRY(probe_fp64(dev, rep));
-
-  rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
-  return 0;
+  });
 }
 
 // 2:4 sparse bf16 GEMM on caller-provided device buffers (convention in
@@ -535,19 +497,18 @@ int cc_attest_fp64(int device, int gemm_dim, struct CcMxReport* rep) {
 int cc_mfma_gemm_sp24(int device, const void* Ac, const void* Am,
                       const void* Bt, void* C, int M, int N, int K,
                       int shape) {
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  int rc = launch_sp24(shape, Ac, Am, Bt, C, M, N, K);
-  if (rc != 0) return rc;
-  return (int)hipDeviceSynchronize();
+  return run_synced(
+      device, [&] { return launch_sp24(shape, Ac, Am, Bt, C, M, N, K); });
 }
 
 // VALU reference of the same convention: any M and N, K a multiple of 8.
 int cc_ref_gemm_sp24_f32(int device, const void* Ac, const void* Am,
                          const void* Bt, void* C, int M, int N, int K) {
   if (M <= 0 || N <= 0 || K <= 0 || K % 8) return -2;
-  if (hipSetDevice(device) != hipSuccess) return -3;
-  launch_ref_sp24(Ac, Am, Bt, C, M, N, K);
-  return (int)hipDeviceSynchronize();
+  return run_synced(device, [&] {
+    launch_ref_sp24(Ac, Am, Bt, C, M, N, K);
+    return 0;
+  });
 }
 
 // The opt-in sparse probe for one SMFMAC shape. gemm_dim below 128 rounds
@@ -558,23 +519,11 @@ int cc_ref_gemm_sp24_f32(int device, const void* Ac, const void* Am,
 // VALU reference bitwise.
 int cc_attest_sparse(int device, int gemm_dim, int shape,
                      struct CcMxReport* rep) {
-  CC_TRY(report_begin(rep, device, [&] {
+  return attest_exact(kLegSparse, device, gemm_dim, {}, shape, rep, [&] {
     if (shape == 0 || shape == 1) return 0;
     snprintf(rep->error, sizeof(rep->error), "shape %d is not 0 or 1", shape);
     return -2;
-  }));
-
-  const int D = gemm_dim < BKS ? BKS : (gemm_dim / BKS) * BKS;
-  rep->mx_m = rep->mx_n = rep->mx_k = D;
-
-  std::lock_guard<std::mutex> lk(g_ctx_mu);
-  DeviceCtx& dev = device_ctx(device);
-  CC_CHECK(dev.events());
-  CC_CHECK(dev.sp24.acquire(D));
-  CC_TRY(probe_sparse(dev, shape, rep));
-
-  rep->ok = (rep->mx_max_abs_err == 0.0f) && (rep->mx_tflops > 0.0) ? 1 : 0;
-  return 0;
+  });
 }
 
 // ABI guard for CcMxReport, as cc_report_sizeof for CcAttestReport.

@@ -125,18 +125,27 @@ static int launch_variant(const GemmVariant& v, const void* A, const void* Bt,
   return v.launch(grid, v.threads, A, Bt, C, M, N, K, arg);
 }
 
+// What the GEMM and reference entry points do on caller-provided buffers:
+// set the device (-3), `launch` (no sync; nonzero: refused, returned as it
+// is), then the synchronise's status.
+template <typename Launch>
+static int run_synced(int device, Launch launch) {
+  if (hipSetDevice(device) != hipSuccess) return -3;
+  int rc = launch();
+  if (rc != 0) return rc;
+  return (int)hipDeviceSynchronize();
+}
+
 // Forced variant: launch, sync. A null `v` (a `which` that names no
 // kernel) is -2 before the device is touched.
 static int run_forced_variant(const GemmVariant* v, int elem_bytes, int device,
                               const void* A, const void* Bt, void* C, int M,
                               int N, int K) {
   if (!v) return -2;
-  if (hipSetDevice(device) != hipSuccess) return -3;
   int arg =
       v->arg == kXcdAuto ? past_infinity_cache(M, N, K, elem_bytes) : v->arg;
-  int rc = launch_variant(*v, A, Bt, C, M, N, K, arg);
-  if (rc != 0) return rc;
-  return (int)hipDeviceSynchronize();
+  return run_synced(
+      device, [&] { return launch_variant(*v, A, Bt, C, M, N, K, arg); });
 }
 
 // Launch the best-fitting bf16 MFMA GEMM variant (no sync).

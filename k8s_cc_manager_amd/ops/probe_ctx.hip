@@ -98,168 +98,60 @@ struct PeerCtx {
   DevBuf<unsigned long long> dPeerSum;
 };
 
-// The MXFP4 leg (cc_attest_mxfp4), same rules as MainCtx.
-struct MxCtx {
-  int dim = 0;
-  int ref_valid = 0;
-  DevBuf<unsigned char> dMxA, dMxB;    // packed fp4
-  DevBuf<unsigned char> dMxSA, dMxSB;  // e8m0
-  DevBuf<float> dMxC, dMxRef, dMxErr;
-  DevBuf<unsigned long long> dMxSum;
-
-  hipError_t acquire(int D) {
-    if (dim == D) return hipSuccess;
-    *this = MxCtx{};
-    const size_t n = (size_t)D * D;
-    hipError_t e;
-    if ((e = dMxA.ensure(n / 2)) || (e = dMxB.ensure(n / 2)) ||
-        (e = dMxSA.ensure(n / 32)) || (e = dMxSB.ensure(n / 32)) ||
-        (e = dMxC.ensure(n * sizeof(float))) ||
-        (e = dMxRef.ensure(n * sizeof(float))) ||
-        (e = dMxErr.ensure(sizeof(float))) ||
-        (e = dMxSum.ensure(sizeof(unsigned long long))))
-      return e;
-    dim = D;
-    return hipSuccess;
-  }
+// What differs between the six exact-GEMM legs (MXFP4, MXFP6, MXFP8, INT8,
+// FP64, 2:4 sparse); probe_exact runs the steps they share. The
+// descriptions are in probe_legs.hip.
+struct ExactCtx;
+struct DeviceCtx;
+enum ExactCompare { kCompareF32, kCompareI32, kCompareF64 };
+struct ExactLeg {
+  ExactCtx DeviceCtx::*ctx;  // the leg's own context
+  int granule;      // gemm_dim rounds down to a multiple, and up to one
+  int op_bytes[4];  // operand buffers: bytes per 32 elements of D x D, 0: none
+  int c_bytes;      // bytes per element of C and of the reference
+  int prefill;      // byte C is filled with before the GEMM writes it
+  ExactCompare compare;
+  int sum_words;  // 32-bit words per element of C that the checksum hashes
+  void (*fill)(const ExactCtx&);
+  // `variant`: the call's MFMA shape where the leg has two. Nonzero: refused.
+  int (*gemm)(const ExactCtx&, int variant);
+  void (*reference)(const ExactCtx&);
 };
 
-// The MXFP6 leg (cc_attest_mxfp6), same rules as MainCtx, keyed by
-// (dim, fmt): the fill and so the cached reference depend on the format.
-struct Mx6Ctx {
-  int dim = 0;
-  int fmt = 0;
-  int ref_valid = 0;
-  DevBuf<unsigned char> dA, dB;    // packed fp6, 3/4 byte per element
-  DevBuf<unsigned char> dSA, dSB;  // e8m0
-  DevBuf<float> dC, dRef, dErr;
-  DevBuf<unsigned long long> dSum;
+// What a leg's cache is keyed by besides dim: the element formats of MXFP6
+// (k0 = fmt) and MXFP8 (k0 = fmt_a, k1 = fmt_b), on which the fills and so
+// the cached reference depend. The per-call variant is not in here: both
+// MFMA shapes of the INT8 and sparse legs read the same fill, so they
+// share the reference.
+struct ExactKey {
+  int k0 = 0, k1 = 0;
+  bool operator==(const ExactKey& o) const { return k0 == o.k0 && k1 == o.k1; }
+};
 
-  hipError_t acquire(int D, int F) {
-    if (dim == D && fmt == F) return hipSuccess;
-    *this = Mx6Ctx{};
-    const size_t n = (size_t)D * D;
+// The context of one exact-GEMM leg, same rules as MainCtx.
+struct ExactCtx {
+  int dim = 0;
+  ExactKey key;
+  int ref_valid = 0;
+  DevBuf<unsigned char> op[4], dC, dRef;
+  DevBuf<unsigned char> dErr;  // max |C - ref|: float, or unsigned for INT8
+  DevBuf<unsigned char> dSum;  // unsigned long long
+
+  hipError_t acquire(const ExactLeg& leg, int D, ExactKey K) {
+    if (dim == D && key == K) return hipSuccess;
+    *this = ExactCtx{};
+    const size_t n = (size_t)D * D;  // D is a multiple of 128
     hipError_t e;
-    if ((e = dA.ensure(n / 4 * 3)) || (e = dB.ensure(n / 4 * 3)) ||
-        (e = dSA.ensure(n / 32)) || (e = dSB.ensure(n / 32)) ||
-        (e = dC.ensure(n * sizeof(float))) ||
-        (e = dRef.ensure(n * sizeof(float))) ||
+    for (int i = 0; i < 4; ++i)
+      if (leg.op_bytes[i] && (e = op[i].ensure(n / 32 * leg.op_bytes[i])))
+        return e;
+    if ((e = dC.ensure(n * leg.c_bytes)) ||
+        (e = dRef.ensure(n * leg.c_bytes)) ||
         (e = dErr.ensure(sizeof(float))) ||
         (e = dSum.ensure(sizeof(unsigned long long))))
       return e;
     dim = D;
-    fmt = F;
-    return hipSuccess;
-  }
-};
-
-// The MXFP8 leg (cc_attest_mxfp8), same rules as MainCtx, keyed by
-// (dim, fa, fb): the fills and so the cached reference depend on both
-// formats.
-struct Mx8Ctx {
-  int dim = 0;
-  int fa = 0, fb = 0;
-  int ref_valid = 0;
-  DevBuf<unsigned char> dA, dB;    // one byte per element
-  DevBuf<unsigned char> dSA, dSB;  // e8m0
-  DevBuf<float> dC, dRef, dErr;
-  DevBuf<unsigned long long> dSum;
-
-  hipError_t acquire(int D, int FA, int FB) {
-    if (dim == D && fa == FA && fb == FB) return hipSuccess;
-    *this = Mx8Ctx{};
-    const size_t n = (size_t)D * D;
-    hipError_t e;
-    if ((e = dA.ensure(n)) || (e = dB.ensure(n)) ||
-        (e = dSA.ensure(n / 32)) || (e = dSB.ensure(n / 32)) ||
-        (e = dC.ensure(n * sizeof(float))) ||
-        (e = dRef.ensure(n * sizeof(float))) ||
-        (e = dErr.ensure(sizeof(float))) ||
-        (e = dSum.ensure(sizeof(unsigned long long))))
-      return e;
-    dim = D;
-    fa = FA;
-    fb = FB;
-    return hipSuccess;
-  }
-};
-
-// The INT8 leg (cc_attest_int8), same rules as MainCtx, keyed by dim
-// alone: both MFMA shapes read the same fill, so they share the cached
-// reference.
-struct I8Ctx {
-  int dim = 0;
-  int ref_valid = 0;
-  DevBuf<signed char> dA, dB;  // one byte per element
-  DevBuf<int> dC, dRef;
-  DevBuf<unsigned> dErr;  // max |C - ref|, an integer
-  DevBuf<unsigned long long> dSum;
-
-  hipError_t acquire(int D) {
-    if (dim == D) return hipSuccess;
-    *this = I8Ctx{};
-    const size_t n = (size_t)D * D;
-    hipError_t e;
-    if ((e = dA.ensure(n)) || (e = dB.ensure(n)) ||
-        (e = dC.ensure(n * sizeof(int))) ||
-        (e = dRef.ensure(n * sizeof(int))) ||
-        (e = dErr.ensure(sizeof(unsigned))) ||
-        (e = dSum.ensure(sizeof(unsigned long long))))
-      return e;
-    dim = D;
-    return hipSuccess;
-  }
-};
-
-// The FP64 leg (cc_attest_fp64), same rules as MainCtx, keyed by dim.
-// 32 bytes per output element (A, B, C and the reference, 8 each): 32 MiB
-// at dim 1024, 2 GiB at the leg's cap of 8192.
-struct F64Ctx {
-  int dim = 0;
-  int ref_valid = 0;
-  DevBuf<double> dA, dB, dC, dRef;
-  DevBuf<float> dErr;  // max |C - ref|, reduced in double
-  DevBuf<unsigned long long> dSum;
-
-  hipError_t acquire(int D) {
-    if (dim == D) return hipSuccess;
-    *this = F64Ctx{};
-    const size_t n = (size_t)D * D * sizeof(double);
-    hipError_t e;
-    if ((e = dA.ensure(n)) || (e = dB.ensure(n)) || (e = dC.ensure(n)) ||
-        (e = dRef.ensure(n)) || (e = dErr.ensure(sizeof(float))) ||
-        (e = dSum.ensure(sizeof(unsigned long long))))
-      return e;
-    dim = D;
-    return hipSuccess;
-  }
-};
-
-// The sparse leg (cc_attest_sparse), same rules as MainCtx, keyed by dim
-// alone: both SMFMAC shapes read the same fill, so they share the cached
-// reference. 11.125 bytes per output element: compressed A (1), its index
-// (1/8), dense B (2), C and the reference (4 each).
-struct Sp24Ctx {
-  int dim = 0;
-  int ref_valid = 0;
-  DevBuf<bf16> dAc, dB;       // [D, D/2] kept values, [D, D] dense
-  DevBuf<unsigned char> dAm;  // [D, D/8] index nibbles
-  DevBuf<float> dC, dRef, dErr;
-  DevBuf<unsigned long long> dSum;
-
-  hipError_t acquire(int D) {
-    if (dim == D) return hipSuccess;
-    *this = Sp24Ctx{};
-    const size_t n = (size_t)D * D;
-    hipError_t e;
-    if ((e = dAc.ensure(n / 2 * sizeof(bf16))) ||
-        (e = dB.ensure(n * sizeof(bf16))) || (e = dAm.ensure(n / 8)) ||
-        (e = dC.ensure(n * sizeof(float))) ||
-        (e = dRef.ensure(n * sizeof(float))) ||
-        (e = dErr.ensure(sizeof(float))) ||
-        (e = dSum.ensure(sizeof(unsigned long long))))
-      return e;
-    dim = D;
+    key = K;
     return hipSuccess;
   }
 };
@@ -306,12 +198,7 @@ struct DeviceCtx {
   bool used = false;  // set by device_ctx(): shutdown has something to free
   MainCtx main;
   PeerCtx peer;
-  MxCtx mx;
-  Mx6Ctx mx6;
-  Mx8Ctx mx8;
-  I8Ctx i8;
-  F64Ctx f64;
-  Sp24Ctx sp24;
+  ExactCtx mx, mx6, mx8, i8, f64, sp24;  // one per exact-GEMM leg
   SweepCtx sweep;
   HbmCtx hbm;
   HostCtx host;

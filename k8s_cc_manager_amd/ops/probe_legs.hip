@@ -1,8 +1,9 @@
 // Probe legs. Each takes the device context and the report and returns
 // 0, a HIP error (text in rep->error) or a negative probe status. The
-// three GEMM legs share the steps that are identical (timed_gemm,
-// cached_reference, compare_read_back); their clears and fills differ
-// and stay in the leg.
+// GEMM legs share the steps that are identical (timed_gemm,
+// cached_reference, compare_read_back). The clears and fills of the bf16
+// and fp8 legs differ and stay in the leg; the six exact-GEMM legs are one
+// routine, probe_exact, and an ExactLeg description each.
 
 // Warm launch, sync, timed launch, TF/s of the D^3 GEMM; -6 when
 // `launch` refuses the shape (returns nonzero).
@@ -33,20 +34,38 @@ static int cached_reference(DeviceCtx& dev, Report* rep, int* valid,
   return 0;
 }
 
-// max_abs_diff of dC against dRef, the checksum of dC where the leg has
-// one, sync, read back.
+// max |dC - dRef| in the element type of `kind`, the checksum of dC where
+// the leg has one, sync, read back. The checksum hashes bit patterns, so
+// it takes any element type as `sum_words` 32-bit words. *err is 0.0 iff
+// every element agrees: the int32 maximum is an integer, converted here.
 template <typename Report>
-static int compare_read_back(Report* rep, const float* dC, const float* dRef,
-                             long elems, float* dErr, float* err,
+static int compare_read_back(Report* rep, const void* dC, const void* dRef,
+                             long elems, void* dErr, float* err,
                              unsigned long long* dSum = nullptr,
-                             unsigned long long* sum = nullptr) {
-  hipLaunchKernelGGL(max_abs_diff, dim3(1024), dim3(256), 0, 0, dC, dRef,
-                     elems, dErr);
+                             unsigned long long* sum = nullptr,
+                             ExactCompare kind = kCompareF32,
+                             int sum_words = 1) {
+  const dim3 grid(1024), block(256);
+  if (kind == kCompareI32)
+    hipLaunchKernelGGL(max_abs_diff_i32, grid, block, 0, 0, (const int*)dC,
+                       (const int*)dRef, elems, (unsigned*)dErr);
+  else if (kind == kCompareF64)
+    hipLaunchKernelGGL(max_abs_diff_f64, grid, block, 0, 0, (const double*)dC,
+                       (const double*)dRef, elems, (float*)dErr);
+  else
+    hipLaunchKernelGGL(max_abs_diff, grid, block, 0, 0, (const float*)dC,
+                       (const float*)dRef, elems, (float*)dErr);
   if (dSum)
-    hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0, dC, elems,
-                       dSum);
+    hipLaunchKernelGGL(checksum_f32, grid, block, 0, 0, (const float*)dC,
+                       sum_words * elems, dSum);
   CC_CHECK(hipDeviceSynchronize());
-  CC_CHECK(read_back(dErr, err));
+  unsigned ierr = 0;
+  if (kind == kCompareI32) {
+    CC_CHECK(read_back(dErr, &ierr));
+    *err = (float)ierr;
+  } else {
+    CC_CHECK(read_back(dErr, err));
+  }
   if (dSum) CC_CHECK(read_back(dSum, sum));
   return 0;
 }
@@ -218,218 +237,179 @@ static int probe_xgmi(DeviceCtx& dev, CcAttestReport* rep) {
   return 0;
 }
 
+// The six exact-GEMM legs, one description each (ExactLeg, probe_ctx.hip).
+// The fills use seed 1u for A and 7u for B, as the bf16 leg does.
+static long exact_elems(const ExactCtx& c) { return (long)c.dim * c.dim; }
+
+// op[2], op[3]: the e8m0 block scales SA and SB of the three MX legs
+static void fill_mx_scales(const ExactCtx& c) {
+  const long n = exact_elems(c) / 32;
+  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, c.op[2].p, n,
+                     1u);
+  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, c.op[3].p, n,
+                     7u);
+}
+
 // MXFP4 leg: all 16 e2m1 codes and scale bytes {126,127,128} through
 // the fp4 decoders and the block-scale hardware, bitwise against the
-// VALU reference (exactness budget at fill_fp4_lcg).
-static int probe_mxfp4(DeviceCtx& dev, CcMxReport* rep) {
-  MxCtx& ctx = dev.mx;
-  const int D = ctx.dim;
-  const long elems = (long)D * D;
-  unsigned char *dA = ctx.dMxA, *dB = ctx.dMxB;
-  unsigned char *dSA = ctx.dMxSA, *dSB = ctx.dMxSB;
-  float *dC = ctx.dMxC, *dRef = ctx.dMxRef, *dErr = ctx.dMxErr;
-  unsigned long long* dSum = ctx.dMxSum;
-  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
-  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
-  // prefill with 0x7f7f7f7f (3.4e38, finite: max_abs_diff's fmaxf would
-  // drop a NaN): an output the kernel never wrote shows as a huge error
-  CC_CHECK(hipMemset(dC, 0x7F, elems * sizeof(float)));
-
-  hipLaunchKernelGGL(fill_fp4_lcg, dim3(2048), dim3(256), 0, 0, dA, elems / 2,
-                     1u);
-  hipLaunchKernelGGL(fill_fp4_lcg, dim3(2048), dim3(256), 0, 0, dB, elems / 2,
-                     7u);
-  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, dSA,
-                     elems / 32, 1u);
-  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, dSB,
-                     elems / 32, 7u);
-
-  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops, [&] {
-    return launch_mxfp4(dA, dSA, dB, dSB, dC, D, D, D);
-  }));
-  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms, [&] {
-    launch_ref_mxfp4(dA, dSA, dB, dSB, dRef, D, D, D);
-  }));
-  return compare_read_back(rep, dC, dRef, elems, dErr, &rep->mx_max_abs_err,
-                           dSum, &rep->mx_checksum);
-}
+// VALU reference (exactness budget at fill_fp4_lcg). op: packed fp4 A, B,
+// then SA, SB. The prefill is 0x7f7f7f7f (3.4e38, finite: max_abs_diff's
+// fmaxf would drop a NaN): an output the kernel never wrote shows as a
+// huge error.
+static const ExactLeg kLegMxfp4 = {
+    &DeviceCtx::mx, BK4, {16, 16, 1, 1}, 4, 0x7F, kCompareF32, 1,
+    [](const ExactCtx& c) {
+      const long n = exact_elems(c) / 2;
+      hipLaunchKernelGGL(fill_fp4_lcg, dim3(2048), dim3(256), 0, 0, c.op[0].p,
+                         n, 1u);
+      hipLaunchKernelGGL(fill_fp4_lcg, dim3(2048), dim3(256), 0, 0, c.op[1].p,
+                         n, 7u);
+      fill_mx_scales(c);
+    },
+    [](const ExactCtx& c, int) {
+      return launch_mxfp4(c.op[0], c.op[2], c.op[1], c.op[3], c.dC, c.dim,
+                          c.dim, c.dim);
+    },
+    [](const ExactCtx& c) {
+      launch_ref_mxfp4(c.op[0], c.op[2], c.op[1], c.op[3], c.dRef, c.dim,
+                       c.dim, c.dim);
+    }};
 
 // MXFP6 leg: the exact magnitude set (fill_fp6_exact) and scale bytes
-// {126,127,128} through the 6-bit decoder of ctx.fmt and the block-scale
-// hardware, bitwise against the VALU reference.
-static int probe_mxfp6(DeviceCtx& dev, CcMxReport* rep) {
-  Mx6Ctx& ctx = dev.mx6;
-  const int D = ctx.dim, fmt = ctx.fmt;
-  const long elems = (long)D * D;
-  unsigned char *dA = ctx.dA, *dB = ctx.dB, *dSA = ctx.dSA, *dSB = ctx.dSB;
-  float *dC = ctx.dC, *dRef = ctx.dRef, *dErr = ctx.dErr;
-  unsigned long long* dSum = ctx.dSum;
-  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
-  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
-  // 0x7f7f7f7f: finite and huge, as in probe_mxfp4
-  CC_CHECK(hipMemset(dC, 0x7F, elems * sizeof(float)));
-
-  hipLaunchKernelGGL(fill_fp6_exact, dim3(1024), dim3(256), 0, 0,
-                     (uint32_t*)dA, elems / 32, 1u, fmt);
-  hipLaunchKernelGGL(fill_fp6_exact, dim3(1024), dim3(256), 0, 0,
-                     (uint32_t*)dB, elems / 32, 7u, fmt);
-  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, dSA,
-                     elems / 32, 1u);
-  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, dSB,
-                     elems / 32, 7u);
-
-  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops, [&] {
-    return launch_mxfp6(fmt, dA, dSA, dB, dSB, dC, D, D, D);
-  }));
-  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms, [&] {
-    launch_ref_mxfp6(fmt, dA, dSA, dB, dSB, dRef, D, D, D);
-  }));
-  return compare_read_back(rep, dC, dRef, elems, dErr, &rep->mx_max_abs_err,
-                           dSum, &rep->mx_checksum);
-}
+// {126,127,128} through the 6-bit decoder of key.k0 (fmt) and the block-scale
+// hardware, bitwise against the VALU reference. op: packed fp6 A, B (3/4
+// byte per element), then SA, SB.
+static const ExactLeg kLegMxfp6 = {
+    &DeviceCtx::mx6, BK6, {24, 24, 1, 1}, 4, 0x7F, kCompareF32, 1,
+    [](const ExactCtx& c) {
+      const long n = exact_elems(c) / 32;
+      hipLaunchKernelGGL(fill_fp6_exact, dim3(1024), dim3(256), 0, 0,
+                         (uint32_t*)c.op[0].p, n, 1u, c.key.k0);
+      hipLaunchKernelGGL(fill_fp6_exact, dim3(1024), dim3(256), 0, 0,
+                         (uint32_t*)c.op[1].p, n, 7u, c.key.k0);
+      fill_mx_scales(c);
+    },
+    [](const ExactCtx& c, int) {
+      return launch_mxfp6(c.key.k0, c.op[0], c.op[2], c.op[1], c.op[3], c.dC,
+                          c.dim, c.dim, c.dim);
+    },
+    [](const ExactCtx& c) {
+      launch_ref_mxfp6(c.key.k0, c.op[0], c.op[2], c.op[1], c.op[3], c.dRef,
+                       c.dim, c.dim, c.dim);
+    }};
 
 // MXFP8 leg: the exact magnitude set (fill_fp8_exact) and scale bytes
-// {126,127,128} through the 8-bit decoders of ctx.fa (A) and ctx.fb (B)
-// and the block-scale hardware, bitwise against the VALU reference.
-static int probe_mxfp8(DeviceCtx& dev, CcMxReport* rep) {
-  Mx8Ctx& ctx = dev.mx8;
-  const int D = ctx.dim, fa = ctx.fa, fb = ctx.fb;
-  const long elems = (long)D * D;
-  unsigned char *dA = ctx.dA, *dB = ctx.dB, *dSA = ctx.dSA, *dSB = ctx.dSB;
-  float *dC = ctx.dC, *dRef = ctx.dRef, *dErr = ctx.dErr;
-  unsigned long long* dSum = ctx.dSum;
-  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
-  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
-  // 0x7f7f7f7f: finite and huge, as in probe_mxfp4
-  CC_CHECK(hipMemset(dC, 0x7F, elems * sizeof(float)));
-
-  hipLaunchKernelGGL(fill_fp8_exact, dim3(2048), dim3(256), 0, 0, dA, elems,
-                     1u, fa);
-  hipLaunchKernelGGL(fill_fp8_exact, dim3(2048), dim3(256), 0, 0, dB, elems,
-                     7u, fb);
-  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, dSA,
-                     elems / 32, 1u);
-  hipLaunchKernelGGL(fill_e8m0_lcg, dim3(256), dim3(256), 0, 0, dSB,
-                     elems / 32, 7u);
-
-  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops, [&] {
-    return launch_mxfp8(fa, fb, dA, dSA, dB, dSB, dC, D, D, D);
-  }));
-  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms, [&] {
-    launch_ref_mxfp8(fa, fb, dA, dSA, dB, dSB, dRef, D, D, D);
-  }));
-  return compare_read_back(rep, dC, dRef, elems, dErr, &rep->mx_max_abs_err,
-                           dSum, &rep->mx_checksum);
-}
+// {126,127,128} through the 8-bit decoders of key.k0 (A's format) and key.k1
+// (B's) and the block-scale hardware, bitwise against the VALU reference.
+// op: A, B (one byte per element), then SA, SB.
+static const ExactLeg kLegMxfp8 = {
+    &DeviceCtx::mx8, BK8, {32, 32, 1, 1}, 4, 0x7F, kCompareF32, 1,
+    [](const ExactCtx& c) {
+      const long n = exact_elems(c);
+      hipLaunchKernelGGL(fill_fp8_exact, dim3(2048), dim3(256), 0, 0,
+                         c.op[0].p, n, 1u, c.key.k0);
+      hipLaunchKernelGGL(fill_fp8_exact, dim3(2048), dim3(256), 0, 0,
+                         c.op[1].p, n, 7u, c.key.k1);
+      fill_mx_scales(c);
+    },
+    [](const ExactCtx& c, int) {
+      return launch_mxfp8(c.key.k0, c.key.k1, c.op[0], c.op[2], c.op[1],
+                          c.op[3], c.dC, c.dim, c.dim, c.dim);
+    },
+    [](const ExactCtx& c) {
+      launch_ref_mxfp8(c.key.k0, c.key.k1, c.op[0], c.op[2], c.op[1], c.op[3],
+                       c.dRef, c.dim, c.dim, c.dim);
+    }};
 
 // INT8 leg: the full byte range -128..127 through the integer MFMA of
 // `shape` (0 = 32x32x32, 1 = 16x16x64), bitwise against the VALU
 // reference, which both shapes share. mx_tflops carries TOP/s and
 // mx_max_abs_err max |C - ref| computed in integers: 0.0 iff every
-// element agrees bitwise.
-static int probe_int8(DeviceCtx& dev, int shape, CcMxReport* rep) {
-  I8Ctx& ctx = dev.i8;
-  const int D = ctx.dim;
-  const long elems = (long)D * D;
-  signed char *dA = ctx.dA, *dB = ctx.dB;
-  int *dC = ctx.dC, *dRef = ctx.dRef;
-  unsigned* dErr = ctx.dErr;
-  unsigned long long* dSum = ctx.dSum;
-  CC_CHECK(hipMemset(dErr, 0, sizeof(unsigned)));
-  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
-  // 0x7f7f7f7f: no sum can reach it while K < 130560, so an output the
-  // kernel never wrote shows as a difference
-  CC_CHECK(hipMemset(dC, 0x7F, elems * sizeof(int)));
-
-  hipLaunchKernelGGL(fill_i8_lcg, dim3(2048), dim3(256), 0, 0, dA, elems, 1u);
-  hipLaunchKernelGGL(fill_i8_lcg, dim3(2048), dim3(256), 0, 0, dB, elems, 7u);
-
-  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops,
-                    [&] { return launch_i8(shape, dA, dB, dC, D, D, D); }));
-  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms,
-                          [&] { launch_ref_i8(dA, dB, dRef, D, D, D); }));
-  hipLaunchKernelGGL(max_abs_diff_i32, dim3(1024), dim3(256), 0, 0, dC, dRef,
-                     elems, dErr);
-  // the checksum hashes bit patterns, so it takes the int32 bits as they are
-  hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0,
-                     (const float*)dC, elems, dSum);
-  CC_CHECK(hipDeviceSynchronize());
-  unsigned err = 0;
-  CC_CHECK(read_back(dErr, &err));
-  CC_CHECK(read_back(dSum, &rep->mx_checksum));
-  rep->mx_max_abs_err = (float)err;
-  return 0;
-}
+// element agrees bitwise. No sum can reach the prefill 0x7f7f7f7f while
+// K < 130560, so an output the kernel never wrote shows as a difference.
+static const ExactLeg kLegInt8 = {
+    &DeviceCtx::i8, BK8, {32, 32}, 4, 0x7F, kCompareI32, 1,
+    [](const ExactCtx& c) {
+      const long n = exact_elems(c);
+      hipLaunchKernelGGL(fill_i8_lcg, dim3(2048), dim3(256), 0, 0,
+                         (signed char*)c.op[0].p, n, 1u);
+      hipLaunchKernelGGL(fill_i8_lcg, dim3(2048), dim3(256), 0, 0,
+                         (signed char*)c.op[1].p, n, 7u);
+    },
+    [](const ExactCtx& c, int shape) {
+      return launch_i8(shape, c.op[0], c.op[1], c.dC, c.dim, c.dim, c.dim);
+    },
+    [](const ExactCtx& c) {
+      launch_ref_i8(c.op[0], c.op[1], c.dRef, c.dim, c.dim, c.dim);
+    }};
 
 // FP64 leg: integer-valued doubles up to 2^20 - 1 through the fp64 MFMA,
 // against the VALU fma reference. Every sum is exact while D <=
 // kF64ExactDim (fill_f64_exact), so the two must be equal:
 // mx_max_abs_err is max |C - ref| taken in double, 0.0 iff every element
-// agrees by value. The compare and the checksum are the leg's own
-// launches, as in probe_int8: compare_read_back is typed for fp32.
-static int probe_fp64(DeviceCtx& dev, CcMxReport* rep) {
-  F64Ctx& ctx = dev.f64;
-  const int D = ctx.dim;
-  const long elems = (long)D * D;
-  double *dA = ctx.dA, *dB = ctx.dB, *dC = ctx.dC, *dRef = ctx.dRef;
-  float* dErr = ctx.dErr;
-  unsigned long long* dSum = ctx.dSum;
-  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
-  CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
-  // all ones is a NaN: an output the kernel never wrote is a mismatch
-  CC_CHECK(hipMemset(dC, 0xFF, elems * sizeof(double)));
-
-  hipLaunchKernelGGL(fill_f64_exact, dim3(2048), dim3(256), 0, 0, dA, elems,
-                     1u);
-  hipLaunchKernelGGL(fill_f64_exact, dim3(2048), dim3(256), 0, 0, dB, elems,
-                     7u);
-
-  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops,
-                    [&] { return launch_f64(dA, dB, dC, D, D, D); }));
-  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms,
-                          [&] { launch_ref_f64(dA, dB, dRef, D, D, D); }));
-  hipLaunchKernelGGL(max_abs_diff_f64, dim3(1024), dim3(256), 0, 0, dC, dRef,
-                     elems, dErr);
-  // the checksum hashes bit patterns: each double as its two 32-bit halves
-  hipLaunchKernelGGL(checksum_f32, dim3(1024), dim3(256), 0, 0,
-                     (const float*)dC, 2 * elems, dSum);
-  CC_CHECK(hipDeviceSynchronize());
-  CC_CHECK(read_back(dErr, &rep->mx_max_abs_err));
-  CC_CHECK(read_back(dSum, &rep->mx_checksum));
-  return 0;
-}
+// agrees by value. The prefill, all ones, is a NaN: an output the kernel
+// never wrote is a mismatch. The checksum takes each double as its two
+// 32-bit halves.
+static const ExactLeg kLegFp64 = {
+    &DeviceCtx::f64, BM, {256, 256}, 8, 0xFF, kCompareF64, 2,
+    [](const ExactCtx& c) {
+      const long n = exact_elems(c);
+      hipLaunchKernelGGL(fill_f64_exact, dim3(2048), dim3(256), 0, 0,
+                         (double*)c.op[0].p, n, 1u);
+      hipLaunchKernelGGL(fill_f64_exact, dim3(2048), dim3(256), 0, 0,
+                         (double*)c.op[1].p, n, 7u);
+    },
+    [](const ExactCtx& c, int) {
+      return launch_f64(c.op[0], c.op[1], c.dC, c.dim, c.dim, c.dim);
+    },
+    [](const ExactCtx& c) {
+      launch_ref_f64(c.op[0], c.op[1], c.dRef, c.dim, c.dim, c.dim);
+    }};
 
 // Sparse leg: the exact value set (fill_sp24_exact) in compressed A and in
 // dense B, all six legal index nibbles, through the SMFMAC of `shape`
 // (0 = 32x32x32, 1 = 16x16x64), bitwise against the VALU reference, which
 // both shapes share. mx_tflops is the dense-equivalent rate, 2 * D^3 over
-// the time: the sparse core does half those multiplies.
-static int probe_sparse(DeviceCtx& dev, int shape, CcMxReport* rep) {
-  Sp24Ctx& ctx = dev.sp24;
+// the time: the sparse core does half those multiplies. op: bf16 Ac
+// [D, D/2] kept values, bf16 B [D, D] dense, Am [D, D/8] index nibbles;
+// 11.125 bytes of VRAM per output element with C and the reference.
+static const ExactLeg kLegSparse = {
+    &DeviceCtx::sp24, BKS, {32, 64, 4}, 4, 0x7F, kCompareF32, 1,
+    [](const ExactCtx& c) {
+      const long n = exact_elems(c);
+      hipLaunchKernelGGL(fill_sp24_exact, dim3(2048), dim3(256), 0, 0,
+                         (bf16*)c.op[0].p, c.op[2].p, n / 8, 1u);
+      hipLaunchKernelGGL(fill_sp24_exact, dim3(2048), dim3(256), 0, 0,
+                         (bf16*)c.op[1].p, (unsigned char*)nullptr, n / 4, 7u);
+    },
+    [](const ExactCtx& c, int shape) {
+      return launch_sp24(shape, c.op[0], c.op[2], c.op[1], c.dC, c.dim, c.dim,
+                         c.dim);
+    },
+    [](const ExactCtx& c) {
+      launch_ref_sp24(c.op[0], c.op[2], c.op[1], c.dRef, c.dim, c.dim, c.dim);
+    }};
+
+// One exact-GEMM leg on its acquired context: clear dErr and dSum, prefill
+// C, fill the operands, GEMM (warm, then timed), the reference unless
+// cached, compare, checksum, sync, read back.
+static int probe_exact(DeviceCtx& dev, const ExactLeg& leg, int variant,
+                       CcMxReport* rep) {
+  ExactCtx& ctx = dev.*leg.ctx;
   const int D = ctx.dim;
-  const long elems = (long)D * D;
-  bf16 *dAc = ctx.dAc, *dB = ctx.dB;
-  unsigned char* dAm = ctx.dAm;
-  float *dC = ctx.dC, *dRef = ctx.dRef, *dErr = ctx.dErr;
-  unsigned long long* dSum = ctx.dSum;
-  CC_CHECK(hipMemset(dErr, 0, sizeof(float)));
+  const long elems = exact_elems(ctx);
+  unsigned long long* dSum = (unsigned long long*)ctx.dSum.p;
+  CC_CHECK(hipMemset(ctx.dErr, 0, sizeof(float)));
   CC_CHECK(hipMemset(dSum, 0, sizeof(unsigned long long)));
-  // 0x7f7f7f7f: finite and huge, as in probe_mxfp4
-  CC_CHECK(hipMemset(dC, 0x7F, elems * sizeof(float)));
-
-  hipLaunchKernelGGL(fill_sp24_exact, dim3(2048), dim3(256), 0, 0, dAc, dAm,
-                     elems / 8, 1u);
-  hipLaunchKernelGGL(fill_sp24_exact, dim3(2048), dim3(256), 0, 0, dB,
-                     (unsigned char*)nullptr, elems / 4, 7u);
-
-  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops, [&] {
-    return launch_sp24(shape, dAc, dAm, dB, dC, D, D, D);
-  }));
-  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms, [&] {
-    launch_ref_sp24(dAc, dAm, dB, dRef, D, D, D);
-  }));
-  return compare_read_back(rep, dC, dRef, elems, dErr, &rep->mx_max_abs_err,
-                           dSum, &rep->mx_checksum);
+  CC_CHECK(hipMemset(ctx.dC, leg.prefill, elems * leg.c_bytes));
+  leg.fill(ctx);
+  CC_TRY(timed_gemm(dev, rep, D, &rep->mx_ms, &rep->mx_tflops,
+                    [&] { return leg.gemm(ctx, variant); }));
+  CC_TRY(cached_reference(dev, rep, &ctx.ref_valid, &rep->mx_ref_ms,
+                          [&] { leg.reference(ctx); }));
+  return compare_read_back(rep, ctx.dC, ctx.dRef, elems, ctx.dErr,
+                           &rep->mx_max_abs_err, dSum, &rep->mx_checksum,
+                           leg.compare, leg.sum_words);
 }
 
 // The golden C images for `rounds`, a constant: computed once per

@@ -194,11 +194,29 @@ def test_device_alive_liveness(attest):
     assert attest.device_alive(0) == 0
 
 
+# The six exact-GEMM legs at their one-tile minimum dim, the smallest at
+# which kernel, fill and reference all still run: (function, dim, kwargs).
+EXACT_LEGS = [
+    ("attest_mxfp4", 256, {}),
+    ("attest_mxfp6", 128, {"fmt": "e2m3"}),
+    ("attest_mxfp8", 128, {"fmt_a": "e4m3", "fmt_b": "e5m2"}),
+    ("attest_int8", 128, {"shape": "32x32x32"}),
+    ("attest_fp64", 128, {}),
+    ("attest_sparse", 128, {"shape": "32x32x32"}),
+]
+
+
+def _run_exact_legs(attest):
+    return [getattr(attest, fn)(0, dim, **kw) for fn, dim, kw in EXACT_LEGS]
+
+
 def test_legs_keep_their_caches_across_main_dim_changes(attest):
     """A change of the main probe's dim frees only the main probe's
-    buffers: the MXFP4 reference, the sweep's golden images and unit
-    table and the liveness word stay."""
-    mx = attest.attest_mxfp4(0, 256)
+    buffers: the references of the six exact-GEMM legs, the sweep's golden
+    images and unit table and the liveness word stay. The six legs share
+    one context type: none of them disturbs another's cache, and the MFMA
+    shape of the INT8 and sparse legs is not part of their key."""
+    first = _run_exact_legs(attest)
     attest.sweep_compute_units(0, rounds=1)
     units = attest.cu_sweep_units(0)
     assert units
@@ -206,16 +224,19 @@ def test_legs_keep_their_caches_across_main_dim_changes(attest):
     assert attest.attest_device(0, 128).ok
     assert attest.attest_device(0, 256).ok
     assert attest.device_alive(0) == 0
-    again = attest.attest_mxfp4(0, 256)
-    assert again.mx_ref_ms == 0.0  # cached reference
-    assert again.mx_checksum == mx.mx_checksum
+    # the other shape shares the reference
+    assert attest.attest_int8(0, 128, shape="16x16x64").mx_ref_ms == 0.0
+    assert attest.attest_sparse(0, 128, shape="16x16x64").mx_ref_ms == 0.0
+    for (fn, _, _), was, now in zip(EXACT_LEGS, first, _run_exact_legs(attest)):
+        assert now.mx_ref_ms == 0.0, fn  # cached reference
+        assert now.mx_checksum == was.mx_checksum, fn
     assert attest.cu_sweep_units(0) == units
     assert attest.sweep_compute_units(0, rounds=1).gold_ms == 0.0  # cached
 
 
 def test_shutdown_frees_every_leg(attest):
     before = attest.attest_device(0, 128)
-    attest.attest_mxfp4(0, 256)
+    _run_exact_legs(attest)
     attest.sweep_compute_units(0, rounds=1)
     assert attest.device_alive(0) == 0
     attest.shutdown()
@@ -223,7 +244,8 @@ def test_shutdown_frees_every_leg(attest):
     after = attest.attest_device(0, 128)
     assert after.ok and after.ref_ms > 0.0  # reference recomputed
     assert after.checksum == before.checksum
-    assert attest.attest_mxfp4(0, 256).mx_ref_ms > 0.0
+    for (fn, _, _), leg in zip(EXACT_LEGS, _run_exact_legs(attest)):
+        assert leg.ok and leg.mx_ref_ms > 0.0, fn  # reference recomputed
     sweep = attest.sweep_compute_units(0, rounds=1)
     assert sweep.ok and sweep.units_failed == 0 and sweep.gold_ms > 0.0
     assert sweep.units_seen == sweep.units_expected
