@@ -444,6 +444,9 @@ _BINDINGS = {
     "cc_mfma_gemm_sp24": (_INT, [_INT] + [_PTR] * 4 + [_INT] * 4),
     "cc_ref_gemm_sp24_f32": (_INT, [_INT] + [_PTR] * 4 + [_INT] * 3),
     "cc_attest_sparse": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CMxReport)]),
+    "cc_mfma_gemm_f16": (_INT, _GEMM + [_INT]),
+    "cc_ref_gemm_f16_f32": (_INT, _GEMM),
+    "cc_attest_fp16": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CMxReport)]),
     "cc_mx_report_sizeof": (_INT, []),
     "cc_cu_sweep": (_INT, [_INT, _INT, _INT, ctypes.POINTER(_CSweepReport)]),
     "cc_cu_sweep_gold": (_INT, [_INT, _INT, ctypes.POINTER(ctypes.c_float)]),
@@ -560,7 +563,7 @@ def _code(table: dict, what: str, value) -> int:
 def _attest_exact(name: str, device_index: int, gemm_dim: int, codes=(),
                   detail: str = "", unit: str = "TF/s",
                   closing: str = "bitwise ok", log_name=None) -> MxReport:
-    """The body of the six exact-GEMM probes: call ``cc_attest_<name>``
+    """The body of the seven exact-GEMM probes: call ``cc_attest_<name>``
     with ``codes`` (format or shape numbers) between gemm_dim and the
     report, raise on rc != 0 and on a report that is not ok, log one
     line. ``detail`` names the codes in the messages."""
@@ -711,6 +714,25 @@ def attest_sparse(device_index: int, gemm_dim: int = 1024,
     return _attest_exact("sparse", device_index, gemm_dim, (code,),
                          f" shape {code}", unit="TF/s dense-equivalent",
                          log_name="2:4 sparse bf16")
+
+
+# the f16 MFMA shapes of the FP16 leg by name; a name's position is the
+# kernel's template argument, which the library takes as it is
+F16_SHAPES = ("32x32x16", "16x16x32")
+_F16_CODES = {name: code for code, name in enumerate(F16_SHAPES)}
+
+
+def attest_fp16(device_index: int, gemm_dim: int = 1024,
+                shape="32x32x16") -> MxReport:
+    """Run the FP16 probe on one GPU for one f16 MFMA shape ("32x32x16" /
+    "16x16x32" or 0 / 1): the IEEE binary16 GEMM on (j/4) * 2^e(row), e over
+    -22..13 (every exponent field, subnormals included, on both operands),
+    against the VALU reference, bitwise. Raises on failure. gemm_dim below
+    128 rounds up to 128, otherwise down to a multiple; above 16384 (K * 961
+    must stay below 2^24) the library refuses it with rc=-2."""
+    code = _code(_F16_CODES, "f16 MFMA shape", shape)
+    return _attest_exact("fp16", device_index, gemm_dim, (code,),
+                         f" shape {code}")
 
 
 CU_SWEEP_MAX_ROUNDS = 256  # exactness cap of the sweep's MFMA chains
@@ -1100,6 +1122,8 @@ _HOOK_EXACT_LEGS = (
     ("FP64", "attest_fp64", [{}], "fp64_tflops", "fp64_exact_ok"),
     ("SPARSE", "attest_sparse", [{"shape": s} for s in SPARSE_SHAPES],
      "sparse_tflops", "sparse_bitwise_ok"),
+    ("FP16", "attest_fp16", [{"shape": s} for s in F16_SHAPES],
+     "fp16_tflops", "fp16_bitwise_ok"),
 )
 
 
@@ -1352,6 +1376,25 @@ def ref_gemm_sp24_f32(device_index: int, ac_ptr: int, am_ptr: int, bt_ptr: int,
     multiply and add in k order, no MFMA): any M and N, K a multiple of 8."""
     _gemm_call("cc_ref_gemm_sp24_f32", "ref_gemm_sp24_f32", device_index,
                ac_ptr, am_ptr, bt_ptr, c_ptr, m, n, k)
+
+
+def mfma_gemm_f16(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
+                  m: int, n: int, k: int, shape="32x32x16") -> None:
+    """FP16 GEMM on the f16 matrix core: C[M,N] fp32 = A[M,K] @ Bt[N,K]^T,
+    A and Bt IEEE binary16 row-major; ``shape`` "32x32x16" (0) or
+    "16x16x32" (1) picks the MFMA. M and N multiples of 128, K of 64,
+    16-byte aligned pointers; anything else raises with rc=-2. Inf and NaN
+    codes are out of scope."""
+    _gemm_call("cc_mfma_gemm_f16", "mfma_gemm_f16", device_index, a_ptr, bt_ptr,
+               c_ptr, m, n, k, _code(_F16_CODES, "f16 MFMA shape", shape))
+
+
+def ref_gemm_f16_f32(device_index: int, a_ptr: int, bt_ptr: int, c_ptr: int,
+                     m: int, n: int, k: int) -> None:
+    """VALU reference of :func:`mfma_gemm_f16` (integer field extraction and
+    ldexpf decode, fp32 fma in k order, no MFMA): any M, N and K above 0."""
+    _gemm_call("cc_ref_gemm_f16_f32", "ref_gemm_f16_f32",
+               device_index, a_ptr, bt_ptr, c_ptr, m, n, k)
 
 
 def ref_gemm_mxfp8_f32(device_index: int, a_ptr: int, sa_ptr: int, bt_ptr: int,

@@ -33,6 +33,10 @@
 //                      mfma_gemm_sp24_128<SHAPE>, compressed A and two
 //                      dense B images in LDS, the index straight from
 //                      global into the lane that uses it;
+//   gemm_f16.hip       FP16 (IEEE binary16) MFMA GEMM with fp32 sums:
+//                      mfma_gemm_f16_128<SHAPE>, the 32x32x16 and the
+//                      16x16x32 f16 op, the int8 kernel's LDS image, each
+//                      32-byte fragment split over two MFMAs;
 //   probe_kernels.hip fills, ref_gemm_f32 (plain VALU fp32 GEMM of the
 //                      same inputs: the independent on-device ground
 //                      truth), the MXFP4 fills and ref_gemm_mxfp4_f32,
@@ -41,6 +45,7 @@
 //                      fill_i8_lcg, ref_gemm_i8_i32 and max_abs_diff_i32,
 //                      fill_f64_exact, ref_gemm_f64 and max_abs_diff_f64,
 //                      fill_sp24_exact and ref_gemm_sp24_f32,
+//                      fill_f16_exact and ref_gemm_f16_f32,
 //                      max-diff, checksum, LDS, HBM, liveness;
 //   cu_sweep.hip       compute-unit sweep: cu_sweep (per-SIMD MFMA chains
 //                      and a whole-LDS march, keyed by the hardware ID
@@ -57,12 +62,12 @@
 //   probe_reports.hip  the five report structs (frozen layouts);
 //   gemm_dispatch.hip  named variants, launchers, production dispatch;
 //   probe_ctx.hip      CC_CHECK / CC_TRY, DevBuf, the per-leg contexts of
-//                      a DeviceCtx (one type, ExactCtx, for the six
+//                      a DeviceCtx (one type, ExactCtx, for the seven
 //                      exact-GEMM legs, with their description ExactLeg),
 //                      timed_ms, read_back, DeviceHop;
 //   host_pattern.hip   the CPU fill and compare of the host-link leg
 //                      (plain C++, no HIP call);
-//   probe_legs.hip     the fifteen legs (six of them one routine,
+//   probe_legs.hip     the sixteen legs (seven of them one routine,
 //                      probe_exact, and an ExactLeg each) and the steps the
 //                      GEMM legs share.
 //
@@ -90,6 +95,9 @@
 // ref_gemm_f64 (v_fma_f64) on data whose every sum is exact, by value.
 // cc_attest_sparse is the structured-sparsity one, one SMFMAC shape per
 // call: the 2:4 sparse bf16 GEMM against ref_gemm_sp24_f32, bitwise.
+// cc_attest_fp16 is the IEEE half-precision one, one f16 MFMA shape
+// (32x32x16 or 16x16x32) per call: the FP16 GEMM over the whole exponent
+// range, subnormals included, against ref_gemm_f16_f32, bitwise.
 // cc_cu_sweep is another: cu_sweep.hip's matrix-core and whole-LDS
 // self-test on every SIMD of every CU, with the units it reached read
 // from the hardware ID registers.
@@ -119,6 +127,7 @@
 #include "gemm_i8.hip"
 #include "gemm_f64.hip"
 #include "gemm_sp24.hip"
+#include "gemm_f16.hip"
 #include "probe_kernels.hip"
 #include "cu_sweep.hip"
 #include "hbm_march.hip"
@@ -161,7 +170,7 @@ static int hbm_refuse_range(Report* rep, unsigned long long origin,
   return -2;
 }
 
-// What the six exact-GEMM probes do once `refuse` has passed (still before
+// What the seven exact-GEMM probes do once `refuse` has passed (still before
 // the device is touched): round gemm_dim to the leg's granule, take the
 // lock, the events and the leg's context for (D, key), run the leg.
 // rep->ok = 1 iff the result equals the reference and the GEMM was timed.
@@ -522,6 +531,44 @@ int cc_attest_sparse(int device, int gemm_dim, int shape,
   return attest_exact(kLegSparse, device, gemm_dim, {}, shape, rep, [&] {
     if (shape == 0 || shape == 1) return 0;
     snprintf(rep->error, sizeof(rep->error), "shape %d is not 0 or 1", shape);
+    return -2;
+  });
+}
+
+// FP16 GEMM on caller-provided device buffers (convention in
+// gemm_f16.hip): IEEE binary16 A[M,K], Bt[N,K], fp32 C[M,N]; shape 0 = the
+// 32x32x16 MFMA, 1 = the 16x16x32 one. M and N multiples of 128, K of 64,
+// pointers 16-byte aligned; anything else returns -2 without launching.
+int cc_mfma_gemm_f16(int device, const void* A, const void* Bt, void* C, int M,
+                     int N, int K, int shape) {
+  return run_synced(
+      device, [&] { return launch_mfma_gemm_f16(shape, A, Bt, C, M, N, K); });
+}
+
+// VALU reference of the same convention (integer field decode, fp32 fma in
+// k order): any M, N and K above 0.
+int cc_ref_gemm_f16_f32(int device, const void* A, const void* Bt, void* C,
+                        int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return -2;
+  return run_synced(device, [&] {
+    launch_ref_gemm_f16_f32(A, Bt, C, M, N, K);
+    return 0;
+  });
+}
+
+// The opt-in FP16 probe for one MFMA shape. gemm_dim below 128 rounds up
+// to 128, otherwise down to a multiple of 128; above kF16ExactDim it is
+// refused, because the leg's sums would no longer be exact. The report is
+// CcMxReport, unchanged: the caller knows the shape. rep->ok = 1 iff the
+// MFMA result equals the VALU reference bitwise.
+int cc_attest_fp16(int device, int gemm_dim, int shape,
+                   struct CcMxReport* rep) {
+  return attest_exact(kLegFp16, device, gemm_dim, {}, shape, rep, [&] {
+    if ((shape == 0 || shape == 1) && gemm_dim <= kF16ExactDim) return 0;
+    snprintf(rep->error, sizeof(rep->error),
+             "shape %d is not 0 or 1, or gemm_dim %d above %d: the fp16 leg's "
+             "sums would not be exact",
+             shape, gemm_dim, kF16ExactDim);
     return -2;
   });
 }

@@ -356,3 +356,33 @@ static void launch_ref_sp24(const void* Ac, const void* Am, const void* Bt,
                      (const unsigned char*)Am, (const bf16*)Bt, (float*)C, M,
                      N, K);
 }
+
+// Launch the FP16 MFMA GEMM (no sync); shape 0 = the 32x32x16 op, 1 = the
+// 16x16x32 op. -2 for any other shape, M or N that is no multiple of the
+// 128 tile, K that is no multiple of the 64-element K-tile, or operands
+// that are not 16-byte aligned. No K cap here: the GEMM rounds like any
+// fp32 accumulate; the exactness cap belongs to the leg (kF16ExactDim).
+static int launch_mfma_gemm_f16(int shape, const void* A, const void* Bt,
+                                void* C, int M, int N, int K) {
+  if (shape != 0 && shape != 1) return -2;
+  if (M <= 0 || N <= 0 || K <= 0 || M % BM || N % BN || K % BK) return -2;
+  if ((((uintptr_t)A | (uintptr_t)Bt | (uintptr_t)C) & 15) != 0) return -2;
+  auto kernel = shape == 0 ? mfma_gemm_f16_128<0> : mfma_gemm_f16_128<1>;
+  hipLaunchKernelGGL(kernel, dim3(N / BN, M / BM), dim3(256), 0, 0,
+                     (const _Float16*)A, (const _Float16*)Bt, (float*)C, M, N,
+                     K);
+  return 0;
+}
+
+static void launch_ref_gemm_f16_f32(const void* A, const void* Bt, void* C,
+                                    int M, int N, int K) {
+  dim3 block(16, 16), grid((N + 15) / 16, (M + 15) / 16);
+  hipLaunchKernelGGL(ref_gemm_f16_f32, grid, block, 0, 0,
+                     (const unsigned short*)A, (const unsigned short*)Bt,
+                     (float*)C, M, N, K);
+}
+
+// Largest dim of the FP16 leg: before the row factors a term of the fill is
+// a multiple of 2^-4 of at most 961/16, so while K * 961 < 2^24 every
+// partial sum fits fp32's 24 bits in any order.
+constexpr int kF16ExactDim = 16384;

@@ -98,8 +98,8 @@ struct PeerCtx {
   DevBuf<unsigned long long> dPeerSum;
 };
 
-// What differs between the six exact-GEMM legs (MXFP4, MXFP6, MXFP8, INT8,
-// FP64, 2:4 sparse); probe_exact runs the steps they share. The
+// What differs between the seven exact-GEMM legs (MXFP4, MXFP6, MXFP8, INT8,
+// FP64, 2:4 sparse, FP16); probe_exact runs the steps they share. The
 // descriptions are in probe_legs.hip.
 struct ExactCtx;
 struct DeviceCtx;
@@ -121,7 +121,7 @@ struct ExactLeg {
 // What a leg's cache is keyed by besides dim: the element formats of MXFP6
 // (k0 = fmt) and MXFP8 (k0 = fmt_a, k1 = fmt_b), on which the fills and so
 // the cached reference depend. The per-call variant is not in here: both
-// MFMA shapes of the INT8 and sparse legs read the same fill, so they
+// MFMA shapes of the INT8, sparse and FP16 legs read the same fill, so they
 // share the reference.
 struct ExactKey {
   int k0 = 0, k1 = 0;
@@ -198,7 +198,7 @@ struct DeviceCtx {
   bool used = false;  // set by device_ctx(): shutdown has something to free
   MainCtx main;
   PeerCtx peer;
-  ExactCtx mx, mx6, mx8, i8, f64, sp24;  // one per exact-GEMM leg
+  ExactCtx mx, mx6, mx8, i8, f64, sp24, f16;  // one per exact-GEMM leg
   SweepCtx sweep;
   HbmCtx hbm;
   HostCtx host;

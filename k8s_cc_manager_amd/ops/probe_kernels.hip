@@ -494,6 +494,83 @@ __global__ void ref_gemm_sp24_f32(const bf16* __restrict__ Ac,
   C[(long)row * N + col] = acc;
 }
 
+// ---------------------------------------------------------------------------
+// FP16 leg: fill and the VALU reference (data convention in gemm_f16.hip
+// and docs/KERNELS.md, "FP16 leg"). The compare is max_abs_diff.
+// ---------------------------------------------------------------------------
+// The row exponent e(r) in -22..13 of fill_f16_exact: r times a unit of
+// the integers mod 36, mod 36, so all 36 values occur inside any 36
+// consecutive rows (and so inside any 128). The unit follows the seed:
+// 5 for the leg's A (seed 1), 23 for its B (seed 7).
+__device__ __forceinline__ int f16_row_exponent(long r, uint32_t seed) {
+  const unsigned char units[12] = {1, 5, 7, 11, 13, 17, 19, 23, 25, 29, 31, 35};
+  return (int)((r * units[seed % 12u]) % 36) - 22;
+}
+
+// rows x cols binary16 codes, element (r, k) = (j/4) * 2^e(r): j uniform
+// in -31..31 from the LCG, whose 64th outcome is the code 0x8000 (-0).
+// 31/4 * 2^13 = 63488 is finite and 1/4 * 2^-22 = 2^-24 is the smallest
+// subnormal, so every element is representable: rows with e(r) < -12 hold
+// subnormals (below -16 nothing else), and the exponent field runs from 0
+// to 30 on both operands.
+// Exactness budget at gemm_f16.hip: bitwise while K <= 16384.
+__global__ void fill_f16_exact(unsigned short* __restrict__ out, int rows,
+                               int cols, uint32_t seed) {
+  const long n = (long)rows * cols;
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  long stride = (long)gridDim.x * blockDim.x;
+  for (; i < n; i += stride) {
+    uint32_t x = (uint32_t)i * 1103515245u + seed * 747796405u + 12345u;
+    x ^= x >> 16;
+    x *= 2654435769u;
+    const unsigned r = (x >> 13) & 63u;
+    unsigned code = 0x8000u;  // r == 63: -0
+    if (r != 63u) {
+      const int j = (int)r - 31;
+      const unsigned m = (unsigned)(j < 0 ? -j : j);  // value m * 2^xp
+      const int xp = f16_row_exponent(i / cols, seed) - 2;
+      code = 0;
+      if (m) {
+        const int p = 31 - __builtin_clz(m);  // m = 1.f * 2^p
+        const int biased = xp + p + 15;
+        code = biased >= 1 ? (unsigned)biased << 10 | ((m << (10 - p)) & 0x3FFu)
+                           : m << (xp + 24);  // subnormal: units of 2^-24
+      }
+      if (j < 0) code |= 0x8000u;
+    }
+    out[i] = (unsigned short)code;
+  }
+}
+
+// the value of a binary16 code: integer field extraction and ldexpf, no
+// conversion instruction. Bias 15, subnormals at exponent 0, Inf and NaN
+// at exponent 31 (IEEE rules).
+__device__ __forceinline__ float f16_value(unsigned code) {
+  const int e = (code >> 10) & 31, m = code & 1023;
+  float v;
+  if (e == 31)
+    v = m ? __builtin_nanf("") : __builtin_inff();
+  else
+    v = ldexpf((float)(e ? 1024 + m : m), (e ? e : 1) - 25);
+  return (code & 0x8000u) ? -v : v;
+}
+
+// VALU fp16 reference GEMM: one thread per C element, fp32 fma in k order
+// (a product of two 11-bit significands is exact in fp32, so fusing
+// changes nothing). No MFMA.
+__global__ void ref_gemm_f16_f32(const unsigned short* __restrict__ A,
+                                 const unsigned short* __restrict__ Bt,
+                                 float* __restrict__ C, int M, int N, int K) {
+  int col = blockIdx.x * blockDim.x + threadIdx.x;
+  int row = blockIdx.y * blockDim.y + threadIdx.y;
+  if (row >= M || col >= N) return;
+  const unsigned short* a = A + (long)row * K;
+  const unsigned short* b = Bt + (long)col * K;
+  float acc = 0.f;
+  for (int k = 0; k < K; ++k) acc = fmaf(f16_value(a[k]), f16_value(b[k]), acc);
+  C[(long)row * N + col] = acc;
+}
+
 // max |x-y| reduction over n elements -> out[0] (pre-zeroed)
 __global__ void max_abs_diff(const float* __restrict__ x,
                              const float* __restrict__ y, long n,

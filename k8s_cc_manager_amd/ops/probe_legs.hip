@@ -2,7 +2,7 @@
 // 0, a HIP error (text in rep->error) or a negative probe status. The
 // GEMM legs share the steps that are identical (timed_gemm,
 // cached_reference, compare_read_back). The clears and fills of the bf16
-// and fp8 legs differ and stay in the leg; the six exact-GEMM legs are one
+// and fp8 legs differ and stay in the leg; the seven exact-GEMM legs are one
 // routine, probe_exact, and an ExactLeg description each.
 
 // Warm launch, sync, timed launch, TF/s of the D^3 GEMM; -6 when
@@ -237,7 +237,7 @@ static int probe_xgmi(DeviceCtx& dev, CcAttestReport* rep) {
   return 0;
 }
 
-// The six exact-GEMM legs, one description each (ExactLeg, probe_ctx.hip).
+// The seven exact-GEMM legs, one description each (ExactLeg, probe_ctx.hip).
 // The fills use seed 1u for A and 7u for B, as the bf16 leg does.
 static long exact_elems(const ExactCtx& c) { return (long)c.dim * c.dim; }
 
@@ -388,6 +388,29 @@ static const ExactLeg kLegSparse = {
     },
     [](const ExactCtx& c) {
       launch_ref_sp24(c.op[0], c.op[2], c.op[1], c.dRef, c.dim, c.dim, c.dim);
+    }};
+
+// FP16 leg: (j/4) * 2^e(row) with e over -22..13 (fill_f16_exact: every
+// exponent field 0..30, subnormals included, on both operands) through the
+// f16 MFMA of `shape` (0 = 32x32x16, 1 = 16x16x32), bitwise against the
+// VALU reference, which both shapes share. The prefill is 0x7f7f7f7f
+// (3.4e38, finite, as for the MX legs: max_abs_diff's fmaxf would drop a
+// NaN); no sum of the fill exceeds 16384 * 961/16 * 2^26 < 2^47, so an
+// output the kernel never wrote shows as a huge error.
+static const ExactLeg kLegFp16 = {
+    &DeviceCtx::f16, BM, {64, 64}, 4, 0x7F, kCompareF32, 1,
+    [](const ExactCtx& c) {
+      hipLaunchKernelGGL(fill_f16_exact, dim3(2048), dim3(256), 0, 0,
+                         (unsigned short*)c.op[0].p, c.dim, c.dim, 1u);
+      hipLaunchKernelGGL(fill_f16_exact, dim3(2048), dim3(256), 0, 0,
+                         (unsigned short*)c.op[1].p, c.dim, c.dim, 7u);
+    },
+    [](const ExactCtx& c, int shape) {
+      return launch_mfma_gemm_f16(shape, c.op[0], c.op[1], c.dC, c.dim, c.dim,
+                                  c.dim);
+    },
+    [](const ExactCtx& c) {
+      launch_ref_gemm_f16_f32(c.op[0], c.op[1], c.dRef, c.dim, c.dim, c.dim);
     }};
 
 // One exact-GEMM leg on its acquired context: clear dErr and dSum, prefill
